@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the SemStereo hot segment (cost volumes + 3-D aggregation + soft-argmax) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch PAIRS_PER_GPU]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch PAIRS_PER_GPU] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus 8 --batch 4                      # BASELINE.json configs[3]: 32 pairs over 8 GPUs
     python bench.py --gpus 8 --height 2048 --width 2048 --maxdisp 192     # configs[4]: 8 pairs over 8 GPUs
@@ -10,9 +10,15 @@ A step = one pass of the hot path (1/4- and 1/8-scale features -> 1/4-scale disp
 reference models/SemStereo.py:273-323) over this rank's batch of synthetic 1024x1024, maxdisp=128
 pairs, inputs resident in HBM.  Pairs are sharded over ranks (weak scaling, no collective inside
 the forward); the timed region is bracketed by barrier + synchronize and the MAX over ranks is
-reported.  Rank 0 prints ONE JSON line with pairs/s, the roofline of the dominant kernel (the
-matrix-core conv of concat_stem: two-term fp16 operands, fp32 accumulate) and of the cost-volume
-build kernel (HBM), EPE against the CPU oracle, and the oracle's own pairs/s on the host cores.
+reported.  A plain run sets up, warms up, times the K steps of the headline leg and rank 0 prints
+ONE JSON line with pairs/s and ms_per_step.  `--full` adds everything else to that line and to the
+detail file: the one-stream leg with the roofline of the dominant kernel (the matrix-core conv of
+concat_stem: two-term fp16 operands, fp32 accumulate) and of the cost-volume build kernel (HBM),
+the steady-state, power, side-configuration, training and other-engine legs, EPE against the CPU
+oracle and the reference fixtures, and the oracle's own pairs/s on the host cores.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32 / float64,
+at most 64 MB in all: a fixed strided sample of a larger output); the inputs and weights are seeded,
+so two builds run with the same arguments can be compared output for output.
 
 Without a launcher (`WORLD_SIZE` unset) and `--gpus N > 1` this file launches its own N ranks: the
 parent makes NO GPU/HIP call, starts N fresh child processes (RANK / LOCAL_RANK / WORLD_SIZE /
@@ -239,7 +245,7 @@ def launch_ranks(n, argv):
 
 def dry_step_factory(device):
     """Stand-in step of `--dry-launch`: a few small CPU matmuls (the launcher rehearsal measures nothing)."""
-    a = torch.randn(64, 64, device=device)
+    a = torch.randn(64, 64, generator=torch.Generator().manual_seed(5), device=device)
 
     def step():
         return {"pred": (a @ a).sum().reshape(1, 1, 1, 1)}
@@ -677,6 +683,36 @@ def float64_truth_leg(seg, oseg, P, cpu_in, feats, out, ref, maxdisp, device):
             "truth_top2_gap_median": gap.median().item(), "seconds": time.perf_counter() - c1}
 
 
+# The headline leg's warm-up lasts at least this long whatever W is.  Before --full existed the one-stream leg always ran first and
+# warmed the chip; without it, K = 20 steps after W = 5 read 589 pairs/s against 600 after that leg on one box (flat on another)
+HEADLINE_WARM_SECONDS = 0.5
+DUMP_BUDGET_BYTES = 64 << 20        # --dump-outputs: every array together
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: the tensors the timed path returned in its last step (the dict a caller of the segment receives), one
+    path/<name>.npy each: float64 where the output is float64 or an integer type, float32 otherwise.  When they come to more than
+    DUMP_BUDGET_BYTES together every array is cut to its share of the budget, one element of each of `keep` equal blocks of its
+    flattened elements at an offset drawn from a seeded generator: the same elements in every run at the same shapes."""
+    import numpy as np
+    arrs = {}
+    for name, t in out.items():
+        if isinstance(t, torch.Tensor):
+            wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+            arrs[name] = t.detach().to("cpu", torch.float64 if wide else torch.float32).numpy()
+    total = sum(a.nbytes for a in arrs.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrs.items():
+        keep = a.size * DUMP_BUDGET_BYTES // total if total > DUMP_BUDGET_BYTES else a.size
+        if keep < a.size:
+            flat = a.reshape(-1)
+            lo = np.arange(keep, dtype=np.int64) * flat.size // keep
+            hi = np.arange(1, keep + 1, dtype=np.int64) * flat.size // keep
+            a = flat[lo + (np.random.default_rng(0).random(keep) * (hi - lo)).astype(np.int64)]
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrs)
+
+
 LINE_BUDGET = 4000          # characters of the JSON line (the driver keeps a 2 000-character tail; VERDICT r3 #5: headline keys inside it)
 
 
@@ -715,7 +751,16 @@ def main():
                     "of ~45 from Python); the per-kernel HIP-event timers are off in this mode")
     ap.add_argument("--dry-launch", action="store_true", help="CPU rehearsal of the N-rank control flow over gloo "
                     "(launcher, rendezvous, barriers, metric reduction, teardown) with a stand-in step; measures nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy "
+                    "(rank 0; float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: the one-stream leg with per-kernel timers and "
+                    "rooflines, the steady-state, power, side-configuration, training and other-engine legs, the CPU baseline and "
+                    "parity, the detail file.  Without it a run times the headline leg alone and the options of those legs do nothing")
     args = ap.parse_args()
+    if not args.full:
+        args.steady_seconds = args.power_seconds = 0
+        args.side_config_steps = args.train_steps = args.parity_pairs = 0
+        args.no_other_engines = args.no_cpu_baseline = args.no_side_rooflines = args.no_kernel_timers = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: become the parent of N ranks BEFORE anything touches the GPU (not even is_available()).  The rendezvous port
@@ -814,13 +859,21 @@ def main():
             return gseg.outputs
         graphed = True
 
-    def timed_run(nsteps, nwarm, kernel_timers=False, min_seconds=0.0):
+    def timed_run(nsteps, nwarm, kernel_timers=False, min_seconds=0.0, warm_seconds=0.0):
         """W untimed + exactly K timed steps (min_seconds > 0: as many whole steps as fit that time, decided by rank 0's clock
         BEFORE the timed region), barrier + synchronize on both sides, MAX over ranks.  The per-kernel HIP events are recorded
-        only inside the timed region.  -> (last output, pairs of all ranks, max seconds, this rank's seconds, steps)."""
+        only inside the timed region.  warm_seconds > 0: more untimed steps after the W until the warm-up has lasted that long.
+        The timed steps visit the input sets in the same order in every leg, so the last step of a leg sees the same inputs
+        whatever ran before it.  -> (last output, pairs of all ranks, max seconds, this rank's seconds, steps)."""
+        t_warm = time.perf_counter()
         for _ in range(nwarm):
             o = step()
         sync()
+        while time.perf_counter() - t_warm < warm_seconds:
+            for _ in range(4):
+                o = step()
+            sync()
+        counter[0] = 0
         if grouped:
             dist.barrier()
         sync()
@@ -838,18 +891,25 @@ def main():
         return o, pairs, tmax, dt_own
 
     # leg 1: every step on the calling stream (W + K steps), with the per-kernel HIP-event timers -> `single_stream`, `roofline`
-    if args.pipelined_only and pipe is not None:
-        out, pairs, tmax, dt_own = timed_run(1, 1)
-    else:
-        out, pairs, tmax, dt_own = timed_run(args.steps, args.warmup, kernel_timers=True)
-    assert M.PATH_COUNTS["torch"] == 0, "a PyTorch fallback ran inside the timed region"
-    single = {"pairs_per_s": pairs / tmax, "ms_per_step": 1e3 * tmax / args.steps} if not args.pipelined_only else None
-    if pipe is not None and not graphed:
+    # (a plain run skips it when leg 2 is the headline)
+    headline_pipelined = pipe is not None and not graphed
+    single = None
+    if args.full or not headline_pipelined:
+        if args.pipelined_only and pipe is not None:
+            out, pairs, tmax, dt_own = timed_run(1, 1)
+        else:
+            out, pairs, tmax, dt_own = timed_run(args.steps, args.warmup, kernel_timers=True,
+                                                 warm_seconds=0.0 if headline_pipelined else HEADLINE_WARM_SECONDS)
+        assert M.PATH_COUNTS["torch"] == 0, "a PyTorch fallback ran inside the timed region"
+        single = {"pairs_per_s": pairs / tmax, "ms_per_step": 1e3 * tmax / args.steps} if not args.pipelined_only else None
+    if headline_pipelined:
         # leg 2, the headline: the same W + K steps issued round-robin on --streams streams (no per-kernel events: they would
         # serialise the lanes)
         use_pipe[0] = True
-        out, pairs, tmax, dt_own = timed_run(args.steps, args.warmup)
+        out, pairs, tmax, dt_own = timed_run(args.steps, args.warmup, warm_seconds=HEADLINE_WARM_SECONDS)
         assert M.PATH_COUNTS["torch"] == 0, "a PyTorch fallback ran inside the timed region"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     # VERDICT r3 #5d: beside the driver's K steps (41 ms at K = 20), a >= 1 s steady-state rate of the same step
     steady = None
@@ -1127,14 +1187,15 @@ def main():
             detail["seeded_pairs_rows"] = rows
             detail["seeded_pairs_oracle_seconds"] = secs
         line["parity"] = parity
-    line["detail"] = os.path.relpath(args.detail, ROOT)
-    detail["line"] = line
-    try:
-        os.makedirs(os.path.dirname(args.detail), exist_ok=True)
-        with open(args.detail, "w") as f:
-            json.dump(detail, f, indent=1)
-    except OSError as e:
-        line["detail"] = f"not written: {e!r}"
+    if args.full:           # (the forensics of the legs a plain run does not run)
+        line["detail"] = os.path.relpath(args.detail, ROOT)
+        detail["line"] = line
+        try:
+            os.makedirs(os.path.dirname(args.detail), exist_ok=True)
+            with open(args.detail, "w") as f:
+                json.dump(detail, f, indent=1)
+        except OSError as e:
+            line["detail"] = f"not written: {e!r}"
 
     def compact(x):
         """6 significant digits for every float of the line (the detail file keeps them all)."""
