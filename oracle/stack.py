@@ -78,7 +78,7 @@ def attention_block(P, key, x, block, num_heads=16):
         # fills are `mask[:, -pad_b:, :]` and `mask[:, :, -pad_r:]`, and "-0:"
         # selects EVERYTHING, so when only one of H/W needs padding the whole
         # flag map is 1 and no logit is masked.
-        is_pad = torch.zeros((H, W), dtype=x.dtype)
+        is_pad = torch.zeros((H, W), dtype=x.dtype, device=x.device)
         is_pad[(H - pad_b) if pad_b > 0 else 0:, :] = 1
         is_pad[:, (W - pad_r) if pad_r > 0 else 0:] = 1
         # per (h,w) window: pad flag of each of its bh*bw pixel columns

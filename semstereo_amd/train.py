@@ -412,6 +412,7 @@ class _UpsampleSoftmaxRegression(torch.autograd.Function):
 
 
 #: SS_SSB_TWO_LAUNCHES=0: the one-launch backward of the probe (rounds 4-5) instead of the two-launch form over a scratch (r06)
+#: (SS_SSB_TWO_LAUNCHES is read once, at import; afterwards only this module attribute switches the form, read at each backward)
 SSB_TWO_LAUNCHES = os.environ.get("SS_SSB_TWO_LAUNCHES", "1") != "0"
 
 

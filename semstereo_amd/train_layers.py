@@ -19,7 +19,8 @@ from .engine import (PATH_COUNTS, conv3d_bf16s_hip, conv3d_head_bf16s_hip, conv3
 
 #: weight-gradient engine of the 3x3x3 layers: "bf16x6" (default, r06: three bf16 terms, six products on the bf16 matrix core,
 #: conv3d_wgrad_bf16s.hip) or "f32" (the exact-fp32 MFMA kernel of rounds 2-5, conv3d_wgrad.hip: 13 TFLOP/s, two thirds of the
-#: training step).  SS_WGRAD_ENGINE; read at call time like the other Python-level switches.
+#: training step).  SS_WGRAD_ENGINE is read once, at import; afterwards only this module attribute switches the engine
+#: (conv3d_wgrad_hip reads it at each call: tests set it with monkeypatch).
 WGRAD_ENGINE = os.environ.get("SS_WGRAD_ENGINE", "bf16x6")
 
 

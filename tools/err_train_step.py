@@ -10,6 +10,7 @@ import os
 import sys
 
 import torch
+import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -44,32 +45,23 @@ for k in sorted(errs, key=errs.get, reverse=True)[:14]: print("%-44s %.2e" % (k,
 print("...")
 for k in sorted(errs, key=errs.get)[:6]: print("%-44s %.2e" % (k, errs[k]))
 
-# ---- which backward kernel is off?  log every _conv_k3_forward / _deconv_k3_forward / wgrad call of a second backward pass and check it in float64
-import torch.nn.functional as F
-M = sa.modules
-log = []
-real_c, real_d, real_w = M._conv_k3_forward, M._deconv_k3_forward, M.conv3d_wgrad_hip
-def spy_c(x, w, stride):
-    y = real_c(x, w, stride)
-    ref = F.conv3d(x.double().cpu(), w.double().cpu(), None, stride, 1)
-    log.append(("conv s%d %s->%s %s" % (stride, w.shape[1], w.shape[0], tuple(x.shape[2:])), float((y.double().cpu() - ref).abs().max()) / (float(ref.abs().max()) + 1e-300)))
-    return y
-def spy_d(x, w):
-    y = real_d(x, w)
-    ref = F.conv_transpose3d(x.double().cpu(), w.double().cpu(), None, stride=2, padding=1, output_padding=1)
-    log.append(("deconv %s->%s %s" % (w.shape[0], w.shape[1], tuple(x.shape[2:])), float((y.double().cpu() - ref).abs().max()) / (float(ref.abs().max()) + 1e-300)))
-    return y
-M._conv_k3_forward, M._deconv_k3_forward = spy_c, spy_d
-seg.zero_grad()
-r = seg(dev(fl4), dev(fr4), dev(fl8), dev(fr8))
-nfwd = len(log)
-(r["pred"].mean() + r["pred_att"].mean()).backward()
-print("forward calls", nfwd, "backward calls", len(log) - nfwd)
-for i, (n, e) in enumerate(log):
-    if e > 2e-6: print("  %s %-40s rel err %.2e" % ("fwd" if i < nfwd else "bwd", n, e))
+# ---- which kernel call is off?  every HIP call of a second pass checked in float64 on its own inputs (tests/train_calls.py: the
+# convolutions at the names _Conv3dK3 / _Deconv3dK3 read in train_layers, and every autograd Function of train.py / ops.py)
+import pytest
+import train_calls as TC
+with pytest.MonkeyPatch.context() as mp:
+    rec = TC.Recorder(sa).install(mp)
+    seg.zero_grad()
+    r = seg(dev(fl4), dev(fr4), dev(fl8), dev(fr8))
+    (r["pred"].mean() + r["pred_att"].mean()).backward()
+    torch.cuda.synchronize()
+print("calls checked:", sum(rec.checked.values()), "of", sum(rec.calls.values()), "; seams not reached:", sorted(TC.STEP_SEAMS - rec.seams_checked()))
+for (seam, part, shape), e in sorted(rec.worst.items(), key=lambda kv: -kv[1]["err"] / kv[1]["bound"])[:12]:
+    print("  %-36s %s %-60s err %.2e (bound %.0e)%s" % (seam, part, shape[:60], e["err"], e["bound"], " conditioning" if e.get("conditioning") else ""))
+print("decided differently:", dict(rec.decisions), "of them unexplained:", dict(rec.unexplained), "; findings:", len(rec.findings))
 
 # ---- do the top-2 picks of regression_topk agree with the oracle's?
-M._conv_k3_forward, M._deconv_k3_forward = real_c, real_d
+M = sa.modules
 cap = {}
 h = seg.classif.register_forward_hook(lambda m, a, o: cap.__setitem__("cost", o.detach().cpu().double()))
 with torch.no_grad():
