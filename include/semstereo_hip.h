@@ -204,6 +204,31 @@ int ss_ssr_upsample_fwd(const float* depth_low, const float* weights, const floa
                         const float* params, float* out, int B, int h, int w, int num_classes,
                         ss_stream_t stream);
 int ss_ssr_param_count(void);
+/* (ABI 20) Its training form, forward and backward on the HIP kernels (csrc/ssr_upsample_train.hip): BatchNorm on batch statistics
+ * (batch_stats = 1: nn.Module.train(), models/submodule.py:412-431 as main_us3d.py:198-206 trains it) or on the running statistics
+ * (batch_stats = 0: eval() under autograd).  n = num_classes = 6 only (SS_ERR_UNSUPPORTED otherwise).
+ *   params: the head's 16 parameter tensors flattened in nn.Module.parameters() order (189 floats: conv.0.weight/bias,
+ *     conv.1.weight/bias, conv.2.weight/bias, conv1.0.weight/bias, conv1.1.weight/bias, conv2.0.weight/bias, conv2.1.weight/bias,
+ *     conv3.weight/bias); grad_params has the same layout and is fully written by the backward.
+ *   saved: 256 floats, 8-byte aligned, written by the forward (float64 mean / invstd of BN0 = conv.0, BNa = conv.2, BN1 = conv1.1,
+ *     BN2 = conv2.1 and the statistics folded into the convolutions) and read by the backward of the same call.
+ *   running statistics (rm*, rv*, nbt*: conv.0, conv.2, conv1.1, conv2.1): with batch_stats = 1 moved inside the kernels as
+ *     F.batch_norm moves them (momentum per layer, variance unbiased, num_batches_tracked += 1; a NULL pointer is left alone);
+ *     with batch_stats = 0 rm* / rv* are the statistics used (required) and nothing is written.
+ *   workspace: float64-aligned scratch of at least 8 * 128 * G bytes (forward) or 8 * 128 * G + 256 + (grad_depth_low ? 28 * N : 0)
+ *     bytes (backward), N = B * 16 * h * w, G = min(ceil(N / 256), 1024).
+ *   grad_depth_low [B,1,h,w], grad_weights / grad_pred_label [B,n,4h,4w]: each NULL = not wanted (not computed / written).
+ * Sums are per-workgroup float64 partials summed in a fixed order: results are bitwise reproducible run to run. */
+int ss_ssr_upsample_train_fwd(const float* depth_low, const float* weights, const float* pred_label, const float* params,
+                              float* out, float* saved, float* rm0, float* rv0, long long* nbt0, float* rma, float* rva,
+                              long long* nbta, float* rm1, float* rv1, long long* nbt1, float* rm2, float* rv2, long long* nbt2,
+                              float eps0, float epsa, float eps1, float eps2, double mom0, double moma, double mom1, double mom2,
+                              int batch_stats, int B, int h, int w, int num_classes, double* workspace, long long workspace_bytes,
+                              ss_stream_t stream);
+int ss_ssr_upsample_train_bwd(const float* depth_low, const float* weights, const float* pred_label, const float* params,
+                              const float* saved, const float* grad_out, float* grad_depth_low, float* grad_weights,
+                              float* grad_pred_label, float* grad_params, int batch_stats, int B, int h, int w, int num_classes,
+                              double* workspace, long long workspace_bytes, ss_stream_t stream);
 
 /* channelAtt gating (models/SemStereo.py:101-102): out[b,c,d,y,x] = sigmoid(att[b,c,y,x]) * cv[b,c,d,y,x] */
 int ss_channel_gate_fwd(const float* att_logits, const float* cv, float* out,

@@ -11,7 +11,7 @@ import torch  # noqa: F401  (must be imported first: it loads the HIP runtime th
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsemstereo_hip.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -45,6 +45,9 @@ _SIGNATURES = {
     "ss_channel_gate_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "ss_channel_att_logits_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "ss_ssr_upsample_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "ss_ssr_upsample_train_fwd": [_P, _P, _P, _P, _P, _P] + [_P] * 12 + [ctypes.c_float] * 4 + [ctypes.c_double] * 4
+                                 + [_I, _I, _I, _I, _I, _P, ctypes.c_longlong, _P],
+    "ss_ssr_upsample_train_bwd": [_P] * 10 + [_I, _I, _I, _I, _I, _P, ctypes.c_longlong, _P],
     "ss_conv3d_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "ss_conv3d_bf16s_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "ss_conv3d_bf16s_partial_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],

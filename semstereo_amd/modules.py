@@ -25,6 +25,7 @@ from . import _lib, ops
 from . import deferred as dfr
 from . import engine as E
 from . import train as T
+from . import train_ssr as TS
 from ._lib import call, ptr
 # the functional layer (engine.py) and the training convolutions (train_layers.py) under their historical names: `modules.X`
 # keeps resolving for every function; the SWITCHES are engine.py's (see __getattr__ at the end of this file)
@@ -692,6 +693,13 @@ class SSR_upsample(nn.Module):
                 call("ss_ssr_upsample_fwd", ptr(depth_low), ptr(weights), ptr(pred_label), ptr(prm), ptr(out),
                      b, h, w, self.num_classes)
             return out
+        if not _inference(self, depth_low, weights, pred_label) and E.TRAIN_HIP and E.SSR_TRAIN_HIP and TS.supported(
+                self, depth_low, weights, pred_label):
+            # train() (batch statistics; also under torch.no_grad()) or eval() under autograd: forward and backward on
+            # ssr_upsample_train.hip, each call with its own gate statistics (nothing parked)
+            PATH_COUNTS["hip_train"] = PATH_COUNTS.get("hip_train", 0) + 1
+            PATH_COUNTS["ssr_train"] = PATH_COUNTS.get("ssr_train", 0) + 1
+            return TS.ssr_train(self, depth_low, weights, pred_label)
         PATH_COUNTS["torch"] += 1
         b, c, h, w = depth_low.shape
         depth_ = F.interpolate(depth_low, (h * 4, w * 4), mode="bilinear").reshape(b, 1, h * 4, w * 4)

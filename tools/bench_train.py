@@ -5,7 +5,11 @@ reference trains its backbone through them) -- at the size the reference trains 
 1024 x 1024 tiles, maxdisp 64, batch 4, Adam lr 1e-3).  Per batch size: ms per step (HIP events around `steps` steps after `warmup`),
 peak allocator memory, finite-gradient and determinism checks, PATH_COUNTS["torch"] unchanged (no PyTorch layer in the 3-D stack).
 Synthetic inputs (bench.py's `synth_features`), random-init weights at unit gain, smooth-L1 losses on `pred` and `pred_att` against a
-synthetic ground truth as `model_loss_train` does for the two 1/4-scale outputs the segment owns.
+synthetic ground truth as `model_loss_train` does for the two 1/4-scale outputs the segment owns.  With --ssr the step also runs the
+SSR_upsample head twice (models/SemStereo.py:311, 324: on pred_att, then on pred, with the same synthetic spx_pred / pred_label, which
+require grad in place of the 2-D producers) and the loss is the four-term model_loss_train (1.0 / 0.6 / 0.5 / 0.3 on pred_up, pred,
+pred_att_up, pred_att; full-resolution targets for the up-sampled outputs).  SS_SSR_TRAIN_HIP=0 runs the head's PyTorch composition
+(usage: add --ssr to any of the command lines below).
 
 usage: python tools/bench_train.py [--batches 1,2,4] [--height 1024 --width 1024 --maxdisp 64] [--steps 5 --warmup 2] [--out gpurun_out/bench_train.json]
        rocprofv3 --kernel-trace --stats ... -- python3 tools/bench_train.py --batches 1 --steps 3 --no-checks      (per-kernel breakdown)
@@ -50,7 +54,7 @@ def family(name):
              ("conv3d_k", "exact-fp32 convs (k = 1, fwd + bwd)"), ("channel_reduce", "BatchNorm statistics / bias gradients"), ("bn_", "BatchNorm apply fwd / bwd"),
              ("window_attention", "windowed attention fwd / bwd"), ("warp", "warp fwd / bwd"), ("gwc", "cost volume fwd / bwd"), ("at::", "PyTorch glue (losses, optimizer, adds)"),
              ("elementwise", "PyTorch glue (losses, optimizer, adds)"), ("vectorized", "PyTorch glue (losses, optimizer, adds)"), ("multi_tensor", "PyTorch glue (losses, optimizer, adds)"),
-             ("reduce_kernel", "PyTorch glue (losses, optimizer, adds)"))
+             ("reduce_kernel", "PyTorch glue (losses, optimizer, adds)"), ("ssr_train", "SSR head (train)"))
     for key, fam in table:
         if key in name:
             return fam
@@ -97,6 +101,7 @@ def main():
                     "to leave its idle power state)")
     ap.add_argument("--no-fused-adam", action="store_true", help="torch.optim.Adam's default (foreach) implementation instead of fused=True")
     ap.add_argument("--no-checks", action="store_true", help="skip the determinism / eval-comparison passes (profiling runs)")
+    ap.add_argument("--ssr", action="store_true", help="also train the SSR_upsample head (two calls, four-term loss)")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "bench_train.json"))
     ap.add_argument("--kernel-stats", default=None)
     args = ap.parse_args()
@@ -116,7 +121,9 @@ def main():
     bench.init_unit_gain(seg, 1234)
     L = conv_layers(H, W, md)
     flops_fwd = sum(2.0 * 27 * ci * co * v for _, kind, ci, co, v in L if kind != "head")
-    res = {"workload": f"{H}x{W} maxdisp={md}, HotSegment.train(): forward + backward + Adam step; features [B,128,H/4,W/4] + [B,256,H/8,W/8] with gradients",
+    head = sa.modules.SSR_upsample(6).to(dev) if args.ssr else None
+    res = {"workload": f"{H}x{W} maxdisp={md}, HotSegment.train(): forward + backward + Adam step; features [B,128,H/4,W/4] + [B,256,H/8,W/8] with gradients"
+                       + (", + SSR_upsample x2 (four-term loss)" if args.ssr else ""), "ssr_train_hip": bool(args.ssr and sa.engine.SSR_TRAIN_HIP),
            "reference": "main_us3d.py:54,74,186-222 (maxdisp 64, batch 4, 1024^2 tiles)", "conv_engine": sa.engine.CONV_ENGINE,
            "gflop_3x3x3_forward_per_pair": flops_fwd / 1e9, "by_batch": {}}
     free0, total = torch.cuda.mem_get_info()
@@ -124,25 +131,39 @@ def main():
         rec = {}
         try:
             seg.train()
+            params = list(seg.parameters()) + (list(head.train().parameters()) if head is not None else [])
             # (the reference: optim.Adam(model.parameters(), lr=args.lr, betas=(0.9, 0.999)), main_us3d.py; `fused`: PyTorch's one-launch
             # implementation of the same update instead of ~6 element-wise launches per parameter tensor)
             try:
-                opt = torch.optim.Adam(seg.parameters(), lr=1e-3, betas=(0.9, 0.999), fused=not args.no_fused_adam)
+                opt = torch.optim.Adam(params, lr=1e-3, betas=(0.9, 0.999), fused=not args.no_fused_adam)
             except (TypeError, RuntimeError):
-                opt = torch.optim.Adam(seg.parameters(), lr=1e-3, betas=(0.9, 0.999))
+                opt = torch.optim.Adam(params, lr=1e-3, betas=(0.9, 0.999))
             fl8, fr8 = bench.synth_features(B, 256, H // 8, W // 8, 6, 5100, dev)
             fl4, fr4 = bench.synth_features(B, 128, H // 4, W // 4, 12, 5200, dev)
             feats = [t.requires_grad_(True) for t in (fl4, fr4, fl8, fr8)]
             g = torch.Generator(device=dev).manual_seed(77)
             gt = (torch.rand(B, H // 4, W // 4, generator=g, device=dev) * 2 - 1) * (md // 4 - 1)
+            if head is not None:
+                gt_full = (torch.rand(B, H, W, generator=g, device=dev) * 2 - 1) * (md - 4)
+                spx = torch.randn(B, 6, H, W, generator=g, device=dev).requires_grad_(True)
+                lab = (2 * torch.randn(B, 6, H, W, generator=g, device=dev)).requires_grad_(True)
+                feats_ssr = [spx, lab]
+            else:
+                feats_ssr = []
             before = dict(sa.modules.PATH_COUNTS)
 
             def step(update=True):
                 opt.zero_grad(set_to_none=True)
-                for t in feats:
+                for t in feats + feats_ssr:
                     t.grad = None
                 r = seg(*feats)
-                loss = F.smooth_l1_loss(r["pred"].squeeze(1), gt) + F.smooth_l1_loss(r["pred_att"], gt)
+                if head is None:
+                    loss = F.smooth_l1_loss(r["pred"].squeeze(1), gt) + F.smooth_l1_loss(r["pred_att"], gt)
+                else:
+                    pred_att_up = head(r["pred_att"].unsqueeze(1), spx, lab)        # models/SemStereo.py:311
+                    pred_up = head(r["pred"], spx, lab)                              # :324
+                    loss = (1.0 * F.smooth_l1_loss(4 * pred_up, gt_full) + 0.6 * F.smooth_l1_loss(r["pred"].squeeze(1), gt)
+                            + 0.5 * F.smooth_l1_loss(4 * pred_att_up, gt_full) + 0.3 * F.smooth_l1_loss(r["pred_att"], gt))
                 loss.backward()
                 if update:
                     opt.step()
@@ -165,17 +186,21 @@ def main():
             torch.cuda.synchronize()
             wall = time.perf_counter() - t0
             ms = e0.elapsed_time(e1) / args.steps
-            assert sa.modules.PATH_COUNTS["torch"] == before["torch"], "a PyTorch layer ran inside the 3-D stack"
+            torch_calls = sa.modules.PATH_COUNTS["torch"] - before["torch"]
+            assert torch_calls == 0 or (head is not None and not sa.engine.SSR_TRAIN_HIP), "a PyTorch layer ran inside the 3-D stack"
             rec.update({"ms_per_step": ms, "pairs_per_s": 1e3 * B / ms, "host_wall_ms_per_step": 1e3 * wall / args.steps,
                         "peak_allocated_gb": torch.cuda.max_memory_allocated() / 2 ** 30, "peak_reserved_gb": torch.cuda.max_memory_reserved() / 2 ** 30,
                         "hip_train_calls_per_step": (sa.modules.PATH_COUNTS.get("hip_train", 0) - before.get("hip_train", 0)) / (n_warm + args.steps),
+                        "ssr_train_calls_per_step": (sa.modules.PATH_COUNTS.get("ssr_train", 0) - before.get("ssr_train", 0)) / (n_warm + args.steps),
+                        "torch_calls_per_step": torch_calls / (n_warm + args.steps),
                         "loss": float(loss),
                         # forward + data gradient + weight gradient of every 3x3x3 layer: 3 x the forward's flops (fp32-equivalent)
                         "fp32_equivalent_tflops_3x3x3": 3.0 * flops_fwd * B / (ms * 1e-3) / 1e12})
             grads = {k: v.grad for k, v in seg.named_parameters() if v.grad is not None}
             rec["parameters_with_gradient"] = len(grads)
             rec["all_gradients_finite"] = bool(all(bool(torch.isfinite(g_).all()) for g_ in grads.values()) and
-                                               all(t.grad is not None and bool(torch.isfinite(t.grad).all()) for t in feats))
+                                               all(t.grad is not None and bool(torch.isfinite(t.grad).all()) for t in feats + feats_ssr) and
+                                               (head is None or all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in head.parameters())))
             if not args.no_checks:
                 # determinism to rounding: the same step twice without a weight update (atomics in the scatter / statistics kernels
                 # reorder fp32 / float64 sums between runs)
@@ -199,7 +224,7 @@ def main():
                     e1.record()
                     torch.cuda.synchronize()
                 rec["inference_ms_per_step_same_shape"] = e0.elapsed_time(e1) / args.steps
-            del opt, feats, grads
+            del opt, feats, grads, feats_ssr
         except torch.OutOfMemoryError as e:       # the largest batch that fits is part of the answer
             rec["error"] = "out of memory: " + str(e)[:160]
         torch.cuda.empty_cache()
