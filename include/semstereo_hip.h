@@ -543,6 +543,43 @@ int ss_sample_strength_bwd_ws(const float* left, const float* right, const float
 int ss_topk_candidates_bwd(const float* logits, const float* strength, const float* samples, const float* grad_att_topk,
                            const float* grad_pred_att, float* grad_logits, float* grad_strength, int B, int dmin, int ndisp, int H, int W,
                            int k, ss_stream_t stream);
+/* ---- the training objective (main_us3d.py:199-208; models/loss.py), csrc/loss.hip ----
+ * Streaming reductions without floating-point atomics: the same inputs give the same bits.  Every result stays on the device: `loss` is
+ * one float, `record` the sums the backward reads (doubles).  `workspace`: ss_loss_workspace_bytes(kind) bytes of scratch, kind 0 = the
+ * disparity loss, 1 = the label / LRSC loss.  Nothing is allocated, copied or synchronised inside. */
+int ss_loss_workspace_bytes(int kind, long long* bytes);
+/* model_loss_train / model_loss_test (models/loss.py:19-31): loss = sum_i w_i * mean over the kept pixels of smooth-L1 (beta 1; l1 = 1:
+ * |.|) of est_i - gt_i, nterms <= 4 terms of n_i elements in one launch.  A pixel is kept where mask_i (a bool tensor) is set or, with
+ * mask_i NULL, where lo <= gt_i < hi (how main_us3d.py:199-200 forms its masks).  record [8]: per term the kept sum and the kept count.
+ * An empty selection gives 0 / 0 = NaN, as PyTorch's mean does. */
+int ss_disparity_loss_fwd(const float* est0, const float* gt0, const unsigned char* mask0, long long n0, const float* est1,
+                          const float* gt1, const unsigned char* mask1, long long n1, const float* est2, const float* gt2,
+                          const unsigned char* mask2, long long n2, const float* est3, const float* gt3, const unsigned char* mask3,
+                          long long n3, float w0, float w1, float w2, float w3, float lo, float hi, int nterms, int l1, double* record,
+                          float* loss, double* workspace, long long workspace_bytes, ss_stream_t stream);
+/* ... backward: grad_i = grad_loss * w_i * clamp(est_i - gt_i, -1, 1) / count_i on kept pixels (sign for l1), 0 elsewhere; grad_i NULL:
+ * that estimate asks for none.  grad_loss: one float on the device. */
+int ss_disparity_loss_bwd(const float* est0, const float* gt0, const unsigned char* mask0, float* grad0, long long n0, const float* est1,
+                          const float* gt1, const unsigned char* mask1, float* grad1, long long n1, const float* est2, const float* gt2,
+                          const unsigned char* mask2, float* grad2, long long n2, const float* est3, const float* gt3,
+                          const unsigned char* mask3, float* grad3, long long n3, float w0, float w1, float w2, float w3, float lo,
+                          float hi, int nterms, int l1, const double* record, const float* grad_loss, ss_stream_t stream);
+/* model_label_loss (models/loss.py:106-119 with dice_loss :33-63): scale * (cross-entropy ignoring class `ignore` + 1 - Dice over batch,
+ * classes 0..C-2 and pixels), logits [B,C,H,W] with C = 6, labels [B,H,W] of label_dtype 0 = int64, 1 = uint8, 2 = float32 (integer
+ * values).  A label outside [0, C) counts as ignored.  record [5]: sum (lse - z_y) over counted pixels, their count, sum p_y over
+ * y < C-1, sum (1 - p_{C-1}), count of y < C-1. */
+int ss_label_loss_fwd(const float* logits, const void* labels, int label_dtype, int B, int num_classes, int H, int W, int ignore, float scale,
+                      double* record, float* loss, double* workspace, long long workspace_bytes, ss_stream_t stream);
+/* ... backward: recomputes the softmax, reads the record; grad_logits [B,C,H,W]. */
+int ss_label_loss_bwd(const float* logits, const void* labels, int label_dtype, int B, int num_classes, int H, int W, int ignore, float scale,
+                      const double* record, const float* grad_loss, float* grad_logits, ss_stream_t stream);
+/* LRSC_loss (models/loss.py:121-135): plain cross-entropy of the right view's logits against the left labels gathered at column
+ * (long) clamp((float) x - disp[b,h,x], 0, W - 1) of the same row, evaluated in fp32 as the reference's tensor expression is.  The same
+ * kernels in their gather mode.  warped (optional, int64 [B,H,W]): the gathered label map.  The disparity gets no gradient. */
+int ss_lrsc_loss_fwd(const float* logits_right, const float* disp, const void* labels, int label_dtype, int B, int num_classes, int H, int W,
+                     double* record, float* loss, long long* warped, double* workspace, long long workspace_bytes, ss_stream_t stream);
+int ss_lrsc_loss_bwd(const float* logits_right, const float* disp, const void* labels, int label_dtype, int B, int num_classes, int H, int W,
+                     const double* record, const float* grad_loss, float* grad_logits, ss_stream_t stream);
 /* Measurement aid (bench.py): a plain device copy, 16 bytes per lane, nontemporal -- the HBM rate a streaming kernel can
  * reach on this box, which SURVEY.md section 8(d) asks the bandwidth fractions to be read against.  bytes % 16 == 0. */
 int ss_tool_copy_fwd(const void* src, void* dst, long long bytes, ss_stream_t stream);

@@ -4,13 +4,15 @@
   modules   nn.Module twins of the 3-D stack with the reference's state_dict keys
   segment   HotSegment: features -> disparities (models/SemStereo.py:273-323)
   install   install(model_module) / accelerate(model): drop-in into the reference's own model
+  losses    the training objective under the reference's names (models/loss.py), install_losses(script_module)
   dist      one-process-per-GPU batch sharding (RCCL / gloo)
 
 The compute lives in csrc/libsemstereo_hip.so behind the C ABI of include/semstereo_hip.h.
 Nothing here falls back to the CPU or to the test oracle.
 """
-from . import _lib, dist, engine, modules, ops, ops_unsigned, segment, train_layers  # noqa: F401
-from .install import accelerate, install, restore_forward, uninstall  # noqa: F401
+from . import _lib, dist, engine, losses, modules, ops, ops_unsigned, segment, train_layers  # noqa: F401
+from .install import accelerate, install, install_losses, restore_forward, uninstall  # noqa: F401
+from .losses import LRSC_loss, model_label_loss, model_loss_test, model_loss_train, train_objective  # noqa: F401
 from .segment import GraphedSegment, HotSegment, PairPipeline  # noqa: F401
 
 __version__ = "0.1.0"

@@ -99,6 +99,13 @@ _SIGNATURES = {
     "ss_channel_gate_bwd_logits": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "ss_window_attention_core_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "ss_window_attention_core_pad_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "ss_loss_workspace_bytes": [_I, _P],
+    "ss_disparity_loss_fwd": [_P, _P, _P, ctypes.c_longlong] * 4 + [ctypes.c_float] * 6 + [_I, _I, _P, _P, _P, ctypes.c_longlong, _P],
+    "ss_disparity_loss_bwd": [_P, _P, _P, _P, ctypes.c_longlong] * 4 + [ctypes.c_float] * 6 + [_I, _I, _P, _P, _P],
+    "ss_label_loss_fwd": [_P, _P, _I, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, ctypes.c_longlong, _P],
+    "ss_label_loss_bwd": [_P, _P, _I, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P],
+    "ss_lrsc_loss_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_longlong, _P],
+    "ss_lrsc_loss_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
 }
 EXPORTS = sorted(list(_SIGNATURES) + ["ss_abi_version", "ss_status_string", "ss_last_hip_error", "ss_ssr_param_count", "ss_reload_tuning"])
 

@@ -42,6 +42,18 @@ def install(model_module, names=ops.REFERENCE_NAMES, unsigned=False):
     return previous
 
 
+def install_losses(script_module):
+    """The objective's counterpart of `install`: the reference's training script imports model_loss_train, model_loss_test,
+    model_label_loss and LRSC_loss into its own globals (main_us3d.py:18) and calls them by bare name (:204-206), so the drop-in is the
+    same rebinding, in the SCRIPT's module.  Returns {name: previous object} for `uninstall`."""
+    from . import losses
+    previous = {}
+    for name in losses.NAMES:
+        previous[name] = getattr(script_module, name, None)
+        setattr(script_module, name, getattr(losses, name))
+    return previous
+
+
 def uninstall(model_module, previous):
     for name, obj in previous.items():
         if obj is None:

@@ -9,7 +9,12 @@ synthetic ground truth as `model_loss_train` does for the two 1/4-scale outputs 
 SSR_upsample head twice (models/SemStereo.py:311, 324: on pred_att, then on pred, with the same synthetic spx_pred / pred_label, which
 require grad in place of the 2-D producers) and the loss is the four-term model_loss_train (1.0 / 0.6 / 0.5 / 0.3 on pred_up, pred,
 pred_att_up, pred_att; full-resolution targets for the up-sampled outputs).  SS_SSR_TRAIN_HIP=0 runs the head's PyTorch composition
-(usage: add --ssr to any of the command lines below).
+(usage: add --ssr to any of the command lines below).  With --ssr --objective the loss is the reference's whole objective
+(main_us3d.py:199-208) through semstereo_amd.train_objective: the four-term disparity loss under the range mask (80 % of the pixels kept),
+the label loss on pred_label against synthetic labels and the LRSC loss on a synthetic right-view logit tensor that requires grad.
+--objective-compare times that step both ways in the same process, alternating round by round: with the objective as a script writes it
+without this package (tools/bench_loss.py: user_objective -- boolean-mask indexing, nn.CrossEntropyLoss, softmax / one_hot Dice) and on
+the HIP kernels; ms per step of each, median / min / max over --rounds.
 
 usage: python tools/bench_train.py [--batches 1,2,4] [--height 1024 --width 1024 --maxdisp 64] [--steps 5 --warmup 2] [--out gpurun_out/bench_train.json]
        rocprofv3 --kernel-trace --stats ... -- python3 tools/bench_train.py --batches 1 --steps 3 --no-checks      (per-kernel breakdown)
@@ -102,6 +107,10 @@ def main():
     ap.add_argument("--no-fused-adam", action="store_true", help="torch.optim.Adam's default (foreach) implementation instead of fused=True")
     ap.add_argument("--no-checks", action="store_true", help="skip the determinism / eval-comparison passes (profiling runs)")
     ap.add_argument("--ssr", action="store_true", help="also train the SSR_upsample head (two calls, four-term loss)")
+    ap.add_argument("--objective", action="store_true", help="with --ssr: the loss is train_objective (masked disparity + label + LRSC loss)")
+    ap.add_argument("--objective-compare", action="store_true", help="with --ssr --objective: also time the step with the objective as a "
+                    "script writes it today, alternating with the HIP one")
+    ap.add_argument("--rounds", type=int, default=5, help="rounds of --objective-compare")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "bench_train.json"))
     ap.add_argument("--kernel-stats", default=None)
     args = ap.parse_args()
@@ -114,6 +123,8 @@ def main():
     import bench
     import semstereo_amd as sa
     assert torch.cuda.is_available(), "bench_train.py needs the MI355X (no CPU path exists)"
+    assert not (args.objective or args.objective_compare) or args.ssr, "--objective needs --ssr (the objective reads the head's outputs)"
+    args.objective = args.objective or args.objective_compare
     sa._lib.load()
     dev = torch.device("cuda")
     H, W, md = args.height, args.width, args.maxdisp
@@ -148,6 +159,15 @@ def main():
                 spx = torch.randn(B, 6, H, W, generator=g, device=dev).requires_grad_(True)
                 lab = (2 * torch.randn(B, 6, H, W, generator=g, device=dev)).requires_grad_(True)
                 feats_ssr = [spx, lab]
+                if args.objective:
+                    import torch.nn as nn
+                    from bench_loss import user_objective
+                    gt_o, gt4_o = [(torch.rand(B, H // q, W // q, generator=g, device=dev) * 2 - 1) * 1.25 * md for q in (1, 4)]   # the mask keeps 80 %
+                    labels = torch.randint(0, 6, (B, H, W), generator=g, device=dev)
+                    lab_r = (2 * torch.randn(B, 6, H, W, generator=g, device=dev)).requires_grad_(True)
+                    feats_ssr.append(lab_r)
+                    objectives = {"hip": sa.train_objective, "user": user_objective(torch, F, nn)}
+                    objective = [objectives["hip"]]
             else:
                 feats_ssr = []
             before = dict(sa.modules.PATH_COUNTS)
@@ -162,8 +182,12 @@ def main():
                 else:
                     pred_att_up = head(r["pred_att"].unsqueeze(1), spx, lab)        # models/SemStereo.py:311
                     pred_up = head(r["pred"], spx, lab)                              # :324
-                    loss = (1.0 * F.smooth_l1_loss(4 * pred_up, gt_full) + 0.6 * F.smooth_l1_loss(r["pred"].squeeze(1), gt)
-                            + 0.5 * F.smooth_l1_loss(4 * pred_att_up, gt_full) + 0.3 * F.smooth_l1_loss(r["pred_att"], gt))
+                    if args.objective:
+                        outs = [4 * pred_up, 4 * r["pred"].squeeze(1), 4 * pred_att_up, 4 * r["pred_att"]]     # models/SemStereo.py:340-344
+                        loss = objective[0](outs, lab, lab_r, gt_o, gt4_o, labels, md, False)[0]
+                    else:
+                        loss = (1.0 * F.smooth_l1_loss(4 * pred_up, gt_full) + 0.6 * F.smooth_l1_loss(r["pred"].squeeze(1), gt)
+                                + 0.5 * F.smooth_l1_loss(4 * pred_att_up, gt_full) + 0.3 * F.smooth_l1_loss(r["pred_att"], gt))
                 loss.backward()
                 if update:
                     opt.step()
@@ -198,6 +222,33 @@ def main():
                         "fp32_equivalent_tflops_3x3x3": 3.0 * flops_fwd * B / (ms * 1e-3) / 1e12})
             grads = {k: v.grad for k, v in seg.named_parameters() if v.grad is not None}
             rec["parameters_with_gradient"] = len(grads)
+            if args.objective:
+                rec["loss_hip_calls_per_step"] = (sa.modules.PATH_COUNTS.get("loss_hip", 0) - before.get("loss_hip", 0)) / (n_warm + args.steps)
+            if args.objective_compare:
+                # the same step with the objective written in PyTorch as a script has it today, and on the kernels, alternating
+                import statistics
+                per = {"user": [], "hip": []}
+                wall_per = {"user": [], "hip": []}
+                for name in per:
+                    objective[0] = objectives[name]
+                    for _ in range(2):
+                        step()
+                for _ in range(args.rounds):
+                    for name in per:
+                        objective[0] = objectives[name]
+                        torch.cuda.synchronize()
+                        tw = time.perf_counter()
+                        e0.record()
+                        for _ in range(args.steps):
+                            step()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        wall_per[name].append(1e3 * (time.perf_counter() - tw) / args.steps)
+                        per[name].append(e0.elapsed_time(e1) / args.steps)
+                objective[0] = objectives["hip"]
+                rec["objective_compare"] = {name: {"ms_per_step": {"median": statistics.median(v), "min": min(v), "max": max(v)},
+                                                   "wall_ms_per_step": {"median": statistics.median(wall_per[name]), "min": min(wall_per[name]),
+                                                                        "max": max(wall_per[name])}} for name, v in per.items()}
             rec["all_gradients_finite"] = bool(all(bool(torch.isfinite(g_).all()) for g_ in grads.values()) and
                                                all(t.grad is not None and bool(torch.isfinite(t.grad).all()) for t in feats + feats_ssr) and
                                                (head is None or all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in head.parameters())))
