@@ -580,6 +580,30 @@ int ss_lrsc_loss_fwd(const float* logits_right, const float* disp, const void* l
                      double* record, float* loss, long long* warped, double* workspace, long long workspace_bytes, ss_stream_t stream);
 int ss_lrsc_loss_bwd(const float* logits_right, const float* disp, const void* labels, int label_dtype, int B, int num_classes, int H, int W,
                      const double* record, const float* grad_loss, float* grad_logits, ss_stream_t stream);
+/* ---- the evaluation step's metrics (main_us3d.py:225-263; utils/metrics.py), csrc/metrics.hip ----
+ * Streaming reductions like the objective's: integer counts, the error sum in double from the wave on, one partial per workgroup, a
+ * second small launch that adds them in a fixed order.  No floating-point atomics, nothing comes back to the host.  `workspace`:
+ * ss_metrics_workspace_bytes(kind) bytes of scratch, kind 0 = the disparity metrics, 1 = the confusion matrix. */
+int ss_metrics_workspace_bytes(int kind, long long* bytes);
+/* EPE_metric / D1_metric / Thres_metric with their per-image wrapper (utils/metrics.py:16-59) and the *_mask variants (:63-89), for
+ * n_est <= 4 estimates [B, pixels_per_image] that share one ground truth, in one pass.  mask (bool) or, with mask NULL, lo <= gt < hi
+ * (main_us3d.py:235) decides which images are skipped (n_mask / n_pos < 0.1, n_pos = #(gt > 0)); the selected pixels are those of
+ * mask_img (bool) or, with mask_img NULL, of the mask.  E = |gt - est| in fp32.
+ *   out    [n_est][2 + n_thr] floats: mean over the kept images of  mean E,  mean (E > 3 & E / |gt| > 0.05),  mean (E > t_k), k < n_thr <= 4;
+ *          0 where no image is kept, NaN where a kept image has an empty selection
+ *   counts [n_est][B][8] int64: n_sel, n_mask, n_pos, n_d1, n_thr[4];   sums [n_est][B] doubles: sum of E over the selection */
+int ss_disparity_metrics_fwd(const float* est0, const float* est1, const float* est2, const float* est3, const float* gt,
+                             const unsigned char* mask, const unsigned char* mask_img, int n_est, int B, long long pixels_per_image,
+                             float lo, float hi, float t0, float t1, float t2, float t3, int n_thr, float* out, long long* counts,
+                             double* sums, void* workspace, long long workspace_bytes, ss_stream_t stream);
+/* SegmentationMetric.get_confusion_matrix (utils/metrics.py:143-168) without its host copy: the joint histogram joint[g][p], int64
+ * [7][6], of the label class g (6 = outside [0, 6)) and p = the first maximum over the 6 channels of logits [B,6,H,W] (a NaN counts as
+ * the maximum, as in np.argmax).  labels: label_dtype 0 = int64, 1 = uint8, 2 = float32 (truncated toward zero), pixel (b, h, x) at
+ * b * label_image_stride + h * label_row_stride + x elements, so a label tensor larger than the logits is cropped without a copy.
+ * accumulate != 0: the counts are added to `joint` (addBatch over an epoch); else `joint` is written.  Other class counts: -2. */
+int ss_seg_confusion_fwd(const float* logits, const void* labels, int label_dtype, int B, int num_classes, int H, int W,
+                         long long label_row_stride, long long label_image_stride, long long* joint, int accumulate, void* workspace,
+                         long long workspace_bytes, ss_stream_t stream);
 /* Measurement aid (bench.py): a plain device copy, 16 bytes per lane, nontemporal -- the HBM rate a streaming kernel can
  * reach on this box, which SURVEY.md section 8(d) asks the bandwidth fractions to be read against.  bytes % 16 == 0. */
 int ss_tool_copy_fwd(const void* src, void* dst, long long bytes, ss_stream_t stream);

@@ -106,6 +106,9 @@ _SIGNATURES = {
     "ss_label_loss_bwd": [_P, _P, _I, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P],
     "ss_lrsc_loss_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_longlong, _P],
     "ss_lrsc_loss_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "ss_metrics_workspace_bytes": [_I, _P],
+    "ss_disparity_metrics_fwd": [_P] * 7 + [_I, _I, ctypes.c_longlong] + [ctypes.c_float] * 6 + [_I, _P, _P, _P, _P, ctypes.c_longlong, _P],
+    "ss_seg_confusion_fwd": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_longlong, ctypes.c_longlong, _P, _I, _P, ctypes.c_longlong, _P],
 }
 EXPORTS = sorted(list(_SIGNATURES) + ["ss_abi_version", "ss_status_string", "ss_last_hip_error", "ss_ssr_param_count", "ss_reload_tuning"])
 

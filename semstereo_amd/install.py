@@ -54,6 +54,18 @@ def install_losses(script_module):
     return previous
 
 
+def install_metrics(script_module):
+    """The evaluation step's counterpart of `install_losses`: the scripts get EPE_metric, D1_metric, Thres_metric, their *_mask variants
+    and SegmentationMetric by `from utils import *` (main_us3d.py:16) and call them by bare name in test_sample (:228, :254-257), so
+    the drop-in is the same rebinding in the SCRIPT's module.  Returns {name: previous object} for `uninstall`."""
+    from . import metrics
+    previous = {}
+    for name in metrics.NAMES:
+        previous[name] = getattr(script_module, name, None)
+        setattr(script_module, name, getattr(metrics, name))
+    return previous
+
+
 def uninstall(model_module, previous):
     for name, obj in previous.items():
         if obj is None:
