@@ -324,6 +324,36 @@ int ss_conv2d_bf16s_fwd(const float* in, const void* wsplit, const float* scale,
 int ss_conv2d_bf16s_pair_fwd(const float* in_a, const float* in_b, const void* wsplit, const float* scale, const float* shift,
                              float* out, int B, int Cin, int H, int W, int Cout, int relu, int nterms, ss_stream_t stream);
 int ss_pack_conv2d_weights_bf16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);
+/* The same layer with its input given as TWO channel ranges: channels [0, Csplit) from x_a [B,Csplit,H,W], [Csplit, Cin) from
+ * rem_a [B,Cin-Csplit,H,W] -- Conv2x's `torch.cat((x, rem), 1)` + conv2 (models/submodule.py:156-160) without the concatenated
+ * tensor.  x_b / rem_b (both or neither): a second view in the same launch (FeatUp applies each Conv2x to the left view, then to the
+ * right one, models/SemStereo.py:74-84): out [2B,Cout,H,W], elements 0..B-1 from the _a pair, B..2B-1 from the _b pair; NULL:
+ * out [B,Cout,H,W].  wsplit is the plain form's (ss_pack_conv2d_weights_f16s / _bf16s of the [Cout,Cin,3,3] weight), and the result
+ * is bit-identical to ss_conv2d_bf16s_fwd on the materialised concatenation at the same launch batch (2B with two views).  As in that
+ * entry point the tile depends on the launch's batch, so two views in one launch may differ from two single launches in the last bits.
+ * Csplit % 8 == 0, else SS_ERR_UNSUPPORTED. */
+int ss_conv2d_bf16s_cat_fwd(const float* x_a, const float* rem_a, const float* x_b, const float* rem_b, const void* wsplit,
+                            const float* scale, const float* shift, float* out, int B, int Csplit, int Cin, int H, int W, int Cout,
+                            int relu, int nterms, ss_stream_t stream);
+/* ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1) + per-channel affine + optional ReLU on [B,Cin,H,W] maps -> out [B,Cout,2H,2W]:
+ * conv1 of every 2-D Conv2x (BasicConv(deconv=True): ConvTranspose2d(bias=False) + BatchNorm2d + ReLU, models/submodule.py:89-116,
+ * 136-138, 150 -- FeatUp's deconv32_16 .. deconv4_2, models/SemStereo.py:63-66, and spx32_16 .. spx4_2, :208-211) with the eval
+ * BatchNorm folded into (scale, shift), and `spx2` (nn.ConvTranspose2d(128, 6, 4, 2, 1) with a bias, models/SemStereo.py:207, 271:
+ * scale NULL, shift = the bias, relu 0).  Four output-parity classes, each a 2x2 convolution (K = 4 Cin) on the two-term fp16
+ * form of the matrix-core engine: nterms must be 19 (anything else: SS_ERR_UNSUPPORTED).  scale / shift may be NULL (1 / 0).
+ * wsplit from ss_pack_deconv2d_weights_f16s.  out must be 8-byte aligned. */
+int ss_deconv2d_bf16s_fwd(const float* in, const void* wsplit, const float* scale, const float* shift, float* out, int B, int Cin,
+                          int H, int W, int Cout, int relu, int nterms, ss_stream_t stream);
+/* The same layer on TWO input tensors in one launch (the two views of FeatUp.forward, models/SemStereo.py:74-84): out
+ * [2B,Cout,2H,2W], elements 0..B-1 from in_a, B..2B-1 from in_b (both [B,Cin,H,W]); every element gets the bits a single launch
+ * gives it. */
+int ss_deconv2d_bf16s_pair_fwd(const float* in_a, const float* in_b, const void* wsplit, const float* scale, const float* shift,
+                               float* out, int B, int Cin, int H, int W, int Cout, int relu, int nterms, ss_stream_t stream);
+/* nn.ConvTranspose2d weight [Cin,Cout,4,4] fp32 (models/submodule.py:104) -> the fragments of ss_deconv2d_bf16s_fwd:
+ * [ceil(Cin/8)][ceil(Cout/32)][4 parity classes][2 tap rows][2 terms][2 tap columns][32 channels][8] fp16 of w scaled per output
+ * channel by a power of two, + float[32 ceil(Cout/32)] of the inverse scales:
+ * ceil(Cin/8) * ceil(Cout/32) * 16384 + 128 * ceil(Cout/32) bytes, 16-byte aligned. */
+int ss_pack_deconv2d_weights_f16s(const float* w, void* wsplit, int Cin, int Cout, ss_stream_t stream);
 /* two-term fp16 form of the 2-D weights (nterms = 19 of ss_conv2d_bf16s_fwd; see ss_pack_conv3d_weights_f16s):
  * ceil(Cin/8)*5*2*2*Cout*16 + 4*Cout bytes. */
 int ss_pack_conv2d_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);

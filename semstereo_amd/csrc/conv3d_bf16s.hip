@@ -178,7 +178,13 @@ typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 // [B][tiles][6][6][34] -- and over the <= 8 tiles that touch an output position in classifier_patch_sum_kernel.  201 MB written +
 // 288 MB read per classifier become 15 + 15 MB; the head's own launch disappears.  `cand` carries the head's fragments
 // (ss_pack_classifier_head_weights), `out` the patch buffer.
-template <int S, int NT, int TD, int TH, int NTERMS, bool GATED, int MT, int KD = 3, int MS = 1, bool ACCB = false, bool GATHER = false, bool HEAD = false>
+//
+// CAT (the 2-D form only): the input's channels [0, csplit) come from `in` (`in2` for batch elements >= bsplit) and [csplit, Cin) from
+// `cand` (`catt` for batch elements >= bsplit), each a contiguous [B,.,H,W] tensor -- Conv2x's torch.cat((x, rem), 1) in front of its
+// 3x3 conv (models/submodule.py:156-160) without the copy.  csplit % 8 == 0, so a staged 8-channel chunk never straddles the two: the
+// chunk loop changes the buffer descriptor at csplit and nothing else; the weights, the K order and therefore the bits are those of
+// the plain form on the materialised concatenation.
+template <int S, int NT, int TD, int TH, int NTERMS, bool GATED, int MT, int KD = 3, int MS = 1, bool ACCB = false, bool GATHER = false, bool HEAD = false, bool CAT = false>
 __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3d_bf16s(const float* __restrict__ in, const uint4* __restrict__ wsplit,
                                                         const float* __restrict__ scale, const float* __restrict__ shift,
                                                         const float* __restrict__ residual, const float* __restrict__ gate,
@@ -186,7 +192,8 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
                                                         int Cin, int D, int H, int W, int Cout, int Do, int Ho, int Wo,
                                                         int tiles_w, int tiles_h, int ntiles, int relu,
                                                         const float* __restrict__ cand, const float* __restrict__ catt,
-                                                        const float* __restrict__ in2, int bsplit) {
+                                                        const float* __restrict__ in2, int bsplit, int csplit) {
+    static_assert(!CAT || (KD == 1 && S == 1 && !GATED && !GATHER && !HEAD), "concat-free form: the plain 2-D tiles");
     static_assert(!GATHER || (S == 1 && MT == 1 && KD == 3 && MS == 1), "gather form: plain stride-1 3-D tiles");
     static_assert(!HEAD || (S == 1 && NT == 4 && TD == 4 && TH == 4 && MT == 1 && KD == 3 && MS == 1 && !GATED && !GATHER && NTERMS == F16X3),
                   "head form: the 4 x 4 x 32 tile of the fp16 engine, one wave per plane");
@@ -279,7 +286,8 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
     const size_t in_plane = (size_t)H * W, chan = GATHER ? in_plane : (size_t)D * in_plane;     // (gather: channels of a 2-D map)
     // (in2: batch elements bsplit, bsplit + 1, ... of the launch come from a SECOND input tensor -- the left and right views of
     // concat_feature in one launch without a torch.cat in front, ss_conv2d_bf16s_pair_fwd)
-    const float* inb = (in2 != nullptr && b >= bsplit) ? in2 + (size_t)(b - bsplit) * Cin * chan : in + (size_t)b * Cin * chan;
+    const int Cin1 = CAT ? csplit : Cin;                        // channels of the (first) input tensor
+    const float* inb = (in2 != nullptr && b >= bsplit) ? in2 + (size_t)(b - bsplit) * Cin1 * chan : in + (size_t)b * Cin1 * chan;
 
     // staging plan of a tile: this thread owns positions p = tid + 256*i of the halo tile, all 8 channels
     auto make_poff = [&](int tile, unsigned (&po)[C::NPOS]) {
@@ -382,7 +390,11 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
     const __amdgpu_buffer_rsrc_t wres = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint4*>(wsplit), 0, (int)min((long long)((Cin + 7) / 8) * KSTEPS * wstep, 0x7fffffffLL), 0x00020000);
     const __amdgpu_buffer_rsrc_t ires = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(inb), 0, (int)min((long long)Cin * (long long)chan * 4, 0x7fffffffLL), 0x00020000);
+        const_cast<float*>(inb), 0, (int)min((long long)Cin1 * (long long)chan * 4, 0x7fffffffLL), 0x00020000);
+    // (CAT: the second tensor's channels, addressed from its own channel 0)
+    const float* inc = !CAT ? inb : ((in2 != nullptr && b >= bsplit) ? catt + (size_t)(b - bsplit) * (Cin - csplit) * chan : cand + (size_t)b * (Cin - csplit) * chan);
+    const __amdgpu_buffer_rsrc_t ires2 = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(inc), 0, CAT ? (int)min((long long)(Cin - csplit) * (long long)chan * 4, 0x7fffffffLL) : 0, 0x00020000);
     const int chan_b = (int)(chan * 4);                                       // bytes per input channel
     auto load_a = [&](int g, int c, int mt) {
         return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(wres, wlane[mt], g * wstep + c * 2 * Cout * 16, 0));
@@ -517,7 +529,9 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
             if (!more) gather_offsets(tile + (int)gridDim.x, poff);
         } else if (!more) make_poff(tile + (int)gridDim.x, poff);          // pure index arithmetic under a wave-uniform branch
         nlive_next = more ? min(8, Cin - ci0 - 8) : min(8, Cin);
-        const int ch_next = more ? ci0 + 8 : 0;
+        int ch_next = more ? ci0 + 8 : 0;
+        const bool second = CAT && ch_next >= csplit;          // workgroup-uniform: the prefetched chunk lies in the second tensor
+        if (CAT && second) ch_next -= csplit;
         const unsigned nomore = (more || has_next) ? 0u : 0x80000000u;
         SS_STAMP_STEPS_BEGIN();
         // ACCB: the chunk's 14 x 3 MFMAs accumulate from ZERO in a second register set that is added to `acc` once per chunk
@@ -577,7 +591,7 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
 #pragma unroll
             for (int q = s * QS; q < (s + 1) * QS && q < NQ; ++q)
                 rin[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                       ires, (int)(poff[q % C::NPOS] | nomore), (ch_next + min(q / C::NPOS, max(nlive_next, 1) - 1)) * chan_b, GATED ? SS_IN_AUX_GATED : SS_IN_AUX));
+                                                       (CAT && second) ? ires2 : ires, (int)(poff[q % C::NPOS] | nomore), (ch_next + min(q / C::NPOS, max(nlive_next, 1) - 1)) * chan_b, GATED ? SS_IN_AUX_GATED : SS_IN_AUX));
 #endif
             uint4 a[MT][NC];
 #pragma unroll
@@ -916,17 +930,17 @@ __global__ __launch_bounds__(256) void pack_weights_f16s_fused_kernel(const floa
 
 #endif  // !SS_CONV_GATHER_TU
 
-template <int S, int NT, int TD, int TH, int NTERMS, bool GATED, int MT, int KD = 3, int MS = 1, bool ACCB = false, bool GATHER = false, bool HEAD = false>
+template <int S, int NT, int TD, int TH, int NTERMS, bool GATED, int MT, int KD = 3, int MS = 1, bool ACCB = false, bool GATHER = false, bool HEAD = false, bool CAT = false>
 int launch_bgm(const float* in, const void* wsplit, const float* scale, const float* shift, const float* residual,
               const float* gate, float* out, int B, int Cin, int D, int H, int W, int Cout, int relu, hipStream_t st,
-              const float* cand = nullptr, const float* catt = nullptr, const float* in2 = nullptr, int bsplit = 0) {
+              const float* cand = nullptr, const float* catt = nullptr, const float* in2 = nullptr, int bsplit = 0, int csplit = 0) {
     using C = BCfg<S, NT, TD, TH, KD, (NTERMS == 6) ? 3 : 2, wlds_form(S, NT, NTERMS, MT, KD, GATHER) ? ((KD * 9 + 1) / 2) * 2 * 64 : 0, MS,
                    gather_slots(GATHER, S, TD, TH, KD) + (HEAD ? HEAD_WSLOTS : 0)>;
     const int Do = (D + 2 * (KD / 2) - KD) / S + 1, Ho = (H - 1) / S + 1, Wo = (W - 1) / S + 1;
     const int tiles_w = ss::ceil_div(Wo, 32), tiles_h = ss::ceil_div(Ho, TH), tiles_d = ss::ceil_div(Do, TD);
     const long long nt = (long long)tiles_w * tiles_h * tiles_d;
     if (nt > 0x7fffffffLL || B > 65535) return SS_ERR_UNSUPPORTED;
-    auto kern = conv3d_bf16s<S, NT, TD, TH, NTERMS, GATED, MT, KD, MS, ACCB, GATHER, HEAD>;
+    auto kern = conv3d_bf16s<S, NT, TD, TH, NTERMS, GATED, MT, KD, MS, ACCB, GATHER, HEAD, CAT>;
     if (C::LDS_BYTES > 64 * 1024) {
         if (ss::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)C::LDS_BYTES) != SS_OK) return SS_ERR_LAUNCH;
     }
@@ -941,7 +955,7 @@ int launch_bgm(const float* in, const void* wsplit, const float* scale, const fl
     // the same time.  Starting the first round's workgroups spread over 0.5-1.5 estimated lifetimes, in 2-16 groups, was
     // measured: no gain, -0 .. -8 %.)
     hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS_BYTES, st, in, reinterpret_cast<const uint4*>(wsplit), scale, shift,
-                       residual, gate, out, Cin, D, H, W, Cout, Do, Ho, Wo, tiles_w, tiles_h, (int)nt, relu, cand, catt, in2, bsplit);
+                       residual, gate, out, Cin, D, H, W, Cout, Do, Ho, Wo, tiles_w, tiles_h, (int)nt, relu, cand, catt, in2, bsplit, csplit);
     return ss::check_launch();
 }
 
@@ -1089,6 +1103,9 @@ extern "C" int ss_pack_conv2d_weights_f16s(const float* w, void* wsplit, int Cou
 static int conv2d_bf16s_impl(const float* in, const float* in2, int bsplit, const void* wsplit, const float* scale, const float* shift,
                             const float* residual, float* out, int B, int Cin, int H, int W, int Cout, int relu,
                             int nterms, ss_stream_t stream);
+static int conv2d_bf16s_cat_impl(const float* x_a, const float* x_b, const float* rem_a, const float* rem_b, int bsplit, int csplit,
+                                const void* wsplit, const float* scale, const float* shift, float* out, int B, int Cin, int H, int W,
+                                int Cout, int relu, int nterms, ss_stream_t stream);
 
 extern "C" int ss_conv2d_bf16s_fwd(const float* in, const void* wsplit, const float* scale, const float* shift,
                                    const float* residual, float* out, int B, int Cin, int H, int W, int Cout, int relu,
@@ -1121,5 +1138,39 @@ static int conv2d_bf16s_impl(const float* in, const float* in2, int bsplit, cons
     if (blocks(8) >= 512) { SS_B2(2, 8); }
     SS_B2(1, 4);
 #undef SS_B2
+}
+
+// The concat-free form (CAT of the kernel): channels [0, Csplit) of the convolution's input from x_a, [Csplit, Cin) from rem_a; with
+// x_b / rem_b the launch serves two views (out [2B,Cout,H,W]: elements 0..B-1 from the _a pair, B..2B-1 from the _b pair).
+extern "C" int ss_conv2d_bf16s_cat_fwd(const float* x_a, const float* rem_a, const float* x_b, const float* rem_b, const void* wsplit,
+                                       const float* scale, const float* shift, float* out, int B, int Csplit, int Cin, int H, int W,
+                                       int Cout, int relu, int nterms, ss_stream_t stream) {
+    SS_REQUIRE(x_a && rem_a && (x_b == nullptr) == (rem_b == nullptr));
+    SS_REQUIRE(B > 0 && Csplit > 0 && Csplit < Cin);
+    if (Csplit % 8 != 0) return SS_ERR_UNSUPPORTED;            // a staged 8-channel chunk would straddle the two tensors
+    const bool pair = x_b != nullptr;
+    return conv2d_bf16s_cat_impl(x_a, x_b, rem_a, rem_b, pair ? B : 0, Csplit, wsplit, scale, shift, out, pair ? 2 * B : B, Cin, H, W, Cout,
+                                 relu, nterms, stream);
+}
+
+static int conv2d_bf16s_cat_impl(const float* x_a, const float* x_b, const float* rem_a, const float* rem_b, int bsplit, int csplit,
+                                const void* wsplit, const float* scale, const float* shift, float* out, int B, int Cin, int H, int W,
+                                int Cout, int relu, int nterms, ss_stream_t stream) {
+    SS_REQUIRE(wsplit && out);
+    SS_REQUIRE(Cin > 0 && H > 0 && W > 0 && Cout > 0 && (nterms == 3 || nterms == 6 || nterms == F16X3));
+    SS_REQUIRE((reinterpret_cast<uintptr_t>(wsplit) & 15) == 0);
+    if ((long long)Cin * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
+    hipStream_t st = ss::as_stream(stream);
+    // (the same tile choice as conv2d_bf16s_impl for the same launch: the two forms are bit-identical)
+    auto blocks = [&](int th) { return (long long)ss::ceil_div(W, 32) * ss::ceil_div(H, th) * ss::ceil_div(Cout, 32) * B; };
+    const int r = relu ? 1 : 0;
+#define SS_B2C(NT, TH)                                                                                                     \
+    return (nterms == 6) ? launch_bgm<1, NT, 1, TH, 6, false, 1, 1, 1, false, false, false, true>(x_a, wsplit, scale, shift, nullptr, nullptr, out, B, Cin, 1, H, W, Cout, r, st, rem_a, rem_b, x_b, bsplit, csplit) \
+         : (nterms == 3) ? launch_bgm<1, NT, 1, TH, 3, false, 1, 1, 1, false, false, false, true>(x_a, wsplit, scale, shift, nullptr, nullptr, out, B, Cin, 1, H, W, Cout, r, st, rem_a, rem_b, x_b, bsplit, csplit) \
+                         : launch_bgm<1, NT, 1, TH, F16X3, false, 1, 1, 1, SS_ACC_BLOCKED != 0, false, false, true>(x_a, wsplit, scale, shift, nullptr, nullptr, out, B, Cin, 1, H, W, Cout, r, st, rem_a, rem_b, x_b, bsplit, csplit)
+    if (blocks(16) >= 512) { SS_B2C(4, 16); }
+    if (blocks(8) >= 512) { SS_B2C(2, 8); }
+    SS_B2C(1, 4);
+#undef SS_B2C
 }
 #endif  // !SS_CONV_GATHER_TU

@@ -453,6 +453,103 @@ def run_conv2d_pair(owner, key, conv, bn, xa, xb, relu):
     return out
 
 
+def run_conv2d_cat(owner, key, conv, bn, xa, rema, relu, xb=None, remb=None):
+    """run_conv2d on torch.cat((xa, rema), 1) WITHOUT the concatenated tensor (ss_conv2d_bf16s_cat_fwd: the chunk loop changes its
+    base pointer at xa's channel count) -- Conv2x's concat + conv2 (models/submodule.py:156-160).  With xb / remb a second view
+    goes through the same launch: -> [2B,Cout,H,W] (first B: the a pair's).  None when it does not apply (the caller concatenates)."""
+    ts = [xa, rema] + ([xb, remb] if xb is not None else [])
+    Cs, Cin = xa.shape[1], xa.shape[1] + rema.shape[1]
+    if not (_decoder_hip_on() and CONV_ENGINE != "f32" and _is_plain_3x3(conv) and conv.in_channels == Cin and Cs % 8 == 0
+            and all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 for t in ts)
+            and xa.shape[0] == rema.shape[0] and xa.shape[2:] == rema.shape[2:]
+            and (xb is None or (xb.shape == xa.shape and remb.shape == rema.shape))):
+        return None
+    nterms = _tiled_nterms()
+    srcs = [conv.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+
+    def build():
+        sc, sh = fold_bn(bn) if bn is not None else (None, None)
+        return pack_conv2d_weight_bf16s(conv.weight, nterms), sc, sh
+    ws, scale, shift = _cache(owner).get(key + "/2d_" + CONV_ENGINE, srcs, build)
+    ts = [t.contiguous() for t in ts]
+    dev = _lib.require_device(*ts, scale, shift)
+    B, _, H, W = xa.shape
+    out = torch.empty(((2 if xb is not None else 1) * B, conv.out_channels, H, W), dtype=xa.dtype, device=xa.device)
+    with torch.cuda.device(dev):
+        call("ss_conv2d_bf16s_cat_fwd", ptr(ts[0]), ptr(ts[1]), ptr(ts[2]) if xb is not None else None, ptr(ts[3]) if xb is not None else None,
+             ptr(ws), ptr(scale), ptr(shift), ptr(out), B, Cs, Cin, H, W, conv.out_channels, int(relu), int(nterms))
+    return out
+
+
+#: the reference's 2-D decoder -- FeatUp's and the spx chain's Conv2x layers and spx2 (models/SemStereo.py:59-86, 207-211) -- on the
+#: 4x4 stride-2 transposed kernel (deconv2d_bf16s.hip) and the concat-free 3x3 instead of MIOpen.  "auto": on for the f16x3 engine
+#: (the transposed kernel has the fp16 form only); SS_DECODER_HIP=0 / 1 forces it.  The twins are swapped in by
+#: `install.accelerate(model, decoder=True)`.
+_dec = os.environ.get("SS_DECODER_HIP", "auto")
+DECODER_HIP = "auto" if _dec == "auto" else (_dec != "0")
+
+
+def _decoder_hip_on():
+    return CONV_ENGINE == "f16x3" if DECODER_HIP == "auto" else bool(DECODER_HIP)
+
+
+def _is_deconv_k4s2(conv):
+    return (isinstance(conv, nn.ConvTranspose2d) and conv.kernel_size == (4, 4) and conv.stride == (2, 2) and conv.padding == (1, 1)
+            and conv.output_padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1)
+
+
+def pack_deconv2d_weight(w):
+    """ConvTranspose2d weight [Cin,Cout,4,4] fp32 -> the fragments of ss_deconv2d_bf16s_fwd (two scaled fp16 terms per parity class +
+    the per-channel inverse scales; int16 tensor, 16-B aligned)."""
+    w = w.detach().float().contiguous()
+    _lib.require_device(w)
+    Cin, Cout = w.shape[0], w.shape[1]
+    assert tuple(w.shape[2:]) == (4, 4)
+    nct = (Cout + 31) // 32
+    out = torch.empty(((Cin + 7) // 8) * nct * 16 * 64 * 8 + 2 * 32 * nct, dtype=torch.int16, device=w.device)
+    with torch.cuda.device(w.device):
+        call("ss_pack_deconv2d_weights_f16s", ptr(w), ptr(out), Cin, Cout)
+    return out
+
+
+def deconv2d_bf16s_hip(x, wsplit, Cout, scale, shift, relu, xb=None):
+    """ConvTranspose2d(k4, s2, p1) + affine + optional ReLU on the two-term fp16 engine; with `xb` both inputs in one launch
+    (-> [2B,Cout,2H,2W], first B: x's)."""
+    x = x if x.is_contiguous() else x.contiguous()
+    dev = _lib.require_device(x, xb, scale, shift)
+    B, Cin, H, W = x.shape
+    out = torch.empty(((2 if xb is not None else 1) * B, Cout, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
+    with torch.cuda.device(dev):
+        if xb is not None:
+            xb = xb if xb.is_contiguous() else xb.contiguous()
+            assert xb.shape == x.shape
+            call("ss_deconv2d_bf16s_pair_fwd", ptr(x), ptr(xb), ptr(wsplit), ptr(scale), ptr(shift), ptr(out), B, Cin, H, W, Cout,
+                 int(relu), 19)
+        else:
+            call("ss_deconv2d_bf16s_fwd", ptr(x), ptr(wsplit), ptr(scale), ptr(shift), ptr(out), B, Cin, H, W, Cout, int(relu), 19)
+    return out
+
+
+def run_deconv2d(owner, key, deconv, bn, x, relu, xb=None):
+    """ConvTranspose2d(k4, s2, p1) [+ BN(eval), or the layer's bias as the shift] [+ ReLU] on the two-term fp16 engine; None when it
+    does not apply (another geometry, the f32 / bf16 engines, SS_DECODER_HIP=0, a CPU tensor)."""
+    if not (_decoder_hip_on() and CONV_ENGINE == "f16x3" and _is_deconv_k4s2(deconv) and x.is_cuda and x.dtype == torch.float32
+            and x.dim() == 4 and x.shape[1] == deconv.in_channels and (bn is None or deconv.bias is None)
+            and (xb is None or (xb.is_cuda and xb.shape == x.shape and xb.dtype == x.dtype))):
+        return None
+    srcs = [deconv.weight] + ([deconv.bias] if deconv.bias is not None else []) + (
+        [bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+
+    def build():
+        if bn is not None:
+            sc, sh = fold_bn(bn)
+        else:
+            sc, sh = None, (deconv.bias.detach().float().contiguous() if deconv.bias is not None else None)
+        return pack_deconv2d_weight(deconv.weight), sc, sh
+    ws, scale, shift = _cache(owner).get(key + "/dc2d_f16s", srcs, build)
+    return deconv2d_bf16s_hip(x, ws, deconv.out_channels, scale, shift, relu, xb)
+
+
 def pack_head_weight_bf16s(w, nterms=6):
     """[1,Cin,3,3,3] fp32 -> split fragments (taps as matrix rows) for ss_conv3d_head_bf16s_fwd: three bf16 terms (nterms 6 / 3)
     or two scaled fp16 terms + the inverse scale (nterms 19)."""
@@ -708,4 +805,4 @@ ATTENTION_FORM = os.environ.get("SS_ATTENTION", "split")      # "split" (3 launc
 
 #: the names tests / tools may SET on this module; `modules.X` forwards reads of them here
 SWITCHES = ("CONV_ENGINE", "DECONV_F16", "DECONV_MIN_WORKGROUPS", "DECONV_BF16S", "CLASSIFIER_CL", "CLASSIFIER_FUSED", "CLASSIFIER_FOLD", "TRAIN_HIP", "SSR_TRAIN_HIP", "LOSS_HIP", "METRICS_HIP", "ATTENTION_FORM",
-            "STEM_LEFT_FUSED", "STEM_PRESPLIT", "STEM_GATHER", "STEM_INPLACE", "HEAD_F16", "CONV2D_HIP")
+            "STEM_LEFT_FUSED", "STEM_PRESPLIT", "STEM_GATHER", "STEM_INPLACE", "HEAD_F16", "CONV2D_HIP", "DECODER_HIP")

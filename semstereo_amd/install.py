@@ -92,14 +92,28 @@ _SWAPS = {
 }
 
 
-def accelerate(model, fuse_forward=False):
+# ... and of the 2-D decoder (FeatUp, the spx chain, spx2: models/SemStereo.py:194, 207-211), swapped by accelerate(decoder=True)
+_DECODER_SWAPS = {
+    "feature_up": M.FeatUp,
+    "spx32_16": M.Conv2x,
+    "spx16_8": M.Conv2x,
+    "spx8_4": M.Conv2x,
+    "spx4_2": M.Conv2x,
+    "spx2": M.Spx2,
+}
+
+
+def accelerate(model, fuse_forward=False, decoder=False):
     """Replace the hot-path sub-modules of a reference `SemStereo` instance (or of the .module of
     its nn.DataParallel wrapper) by HIP-backed twins that SHARE its parameters; state_dict keys and
     values are unchanged.  With `fuse_forward` the instance's forward is additionally routed through
-    `fused_inference_forward` for inference calls.  Returns the list of swapped attribute names."""
+    `fused_inference_forward` for inference calls.  With `decoder` the 2-D decoder (`feature_up`, `spx32_16` .. `spx4_2`, `spx2`)
+    is swapped too: its 4x4 stride-2 transposed convs and concat + 3x3 convs then run on HIP kernels in inference (SS_DECODER_HIP).
+    Returns the list of swapped attribute names."""
     target = model.module if isinstance(model, nn.DataParallel) else model
     done = []
-    for name, cls in _SWAPS.items():
+    swaps = list(_SWAPS.items()) + (list(_DECODER_SWAPS.items()) if decoder else [])
+    for name, cls in swaps:
         sub = getattr(target, name, None)
         if sub is None or isinstance(sub, cls):
             continue

@@ -9,6 +9,9 @@ attribute structure and state_dict keys/shapes as the reference, so its checkpoi
   channelAtt         models/SemStereo.py:89-103
   Classifier         the nn.Sequential(convbn_3d, ReLU, Conv3d) heads, models/SemStereo.py:228-234
   DepthwisePatch     the `patch` nn.Conv3d, models/SemStereo.py:219
+  Conv2x             models/submodule.py:119-161      (the 2-D decoder; swapped in by accelerate(decoder=True))
+  FeatUp             models/SemStereo.py:59-86
+  Spx2               the `spx2` nn.Sequential(ConvTranspose2d), models/SemStereo.py:207
 
 The torch layers inside (nn.Conv3d, nn.BatchNorm3d, ...) are parameter containers: in inference
 (`eval()` and no autograd) forward() runs the gfx950 kernels with BatchNorm folded into the
@@ -758,6 +761,174 @@ def drop_parked_gates(model=None):
     for m_ in model.modules():
         if isinstance(m_, SSR_upsample):
             _GATE_PARKED.pop(m_, None)
+
+
+# --------------------------------------------------------------------------------------
+# the 2-D decoder: Conv2x, FeatUp, spx2 (models/submodule.py:119-161, models/SemStereo.py:59-86, 207-211)
+# --------------------------------------------------------------------------------------
+
+def _stock_basicconv(bc, x):
+    """The reference's BasicConv.forward (models/submodule.py:109-116) on the stock PyTorch layers."""
+    PATH_COUNTS["torch"] += 1
+    x = bc.conv(x)
+    if bc.use_bn:
+        x = bc.bn(x)
+    if bc.relu:
+        x = F.relu(x)
+    return x
+
+
+class Conv2x(nn.Module):
+    """Conv2x (models/submodule.py:119-161): BasicConv(stride 2; 4x4 transposed when `deconv`) -> cat with / add to the skip map ->
+    BasicConv(3x3); keys `conv1.conv.weight`, `conv1.bn.*`, `conv2.conv.weight`, `conv2.bn.*`.  Inference of the 2-D transposed,
+    concatenating form with matching shapes -- every Conv2x of FeatUp and of the spx chain -- runs the 4x4 stride-2 transposed
+    kernel and the concat-free 3x3 (no torch.cat); everything else (autograd, CPU, the 3-D form, concat=False, keep_dispc, a skip
+    map of another size, the f32 engine, SS_DECODER_HIP=0) runs the reference's own statements on the stock layers."""
+
+    def __init__(self, in_channels, out_channels, deconv=False, is_3d=False, concat=True, keep_concat=True, bn=True, relu=True, keep_dispc=False):
+        super().__init__()
+        self.concat = concat
+        self.is_3d = is_3d
+        if deconv and is_3d:
+            kernel = (4, 4, 4)
+        elif deconv:
+            kernel = 4
+        else:
+            kernel = 3
+        if deconv and is_3d and keep_dispc:
+            self.conv1 = BasicConv(in_channels, out_channels, deconv, is_3d, bn=True, relu=True, kernel_size=(1, 4, 4), stride=(1, 2, 2), padding=(0, 1, 1))
+        else:
+            self.conv1 = BasicConv(in_channels, out_channels, deconv, is_3d, bn=True, relu=True, kernel_size=kernel, stride=2, padding=1)
+        if self.concat:
+            mul = 2 if keep_concat else 1
+            self.conv2 = BasicConv(out_channels * 2, out_channels * mul, False, is_3d, bn, relu, kernel_size=3, stride=1, padding=1)
+        else:
+            self.conv2 = BasicConv(out_channels, out_channels, False, is_3d, bn, relu, kernel_size=3, stride=1, padding=1)
+
+    @classmethod
+    def adopt(cls, ref):
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.concat, self.is_3d = ref.concat, ref.is_3d
+        self.conv1, self.conv2 = ref.conv1, ref.conv2          # (parameter containers: .conv, .bn, .use_bn, .relu are read directly)
+        self.train(ref.training)
+        return self
+
+    def _hip_applies(self, *xs):
+        a, b = self.conv1, self.conv2
+        return (self.concat and not self.is_3d and E._decoder_hip_on() and E.CONV_ENGINE == "f16x3"
+                and E._is_deconv_k4s2(a.conv) and a.conv.bias is None and a.use_bn and a.relu and _is_plain_3x3(b.conv)
+                and all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 for t in xs)
+                and _inference(self, *xs))
+
+    def _conv2_after_hip_deconv(self, y, rem, xb=None, remb=None):
+        """conv2 on cat(y, rem) [and on cat(xb, remb)] behind the transposed kernel: the concat-free launch, or -- where that declines
+        (the deconv's channels are not a multiple of 8) -- the plain 3x3 on the materialised concatenation."""
+        b = self.conv2
+        bn2 = b.bn if b.use_bn else None
+        z = E.run_conv2d_cat(b, "bc2d", b.conv, bn2, y, rem, bool(b.relu), xb=xb, remb=remb)
+        if z is not None:
+            return (z,) if xb is None else (z[:y.shape[0]], z[y.shape[0]:])
+        outs = []
+        for u, r in ((y, rem),) + (((xb, remb),) if xb is not None else ()):
+            c = torch.cat((u, r), 1)
+            v = run_conv2d(b, "bc2d", b.conv, bn2, c, bool(b.relu))
+            outs.append(v if v is not None else _stock_basicconv(b, c))
+        return tuple(outs)
+
+    def forward(self, x, rem):
+        x, rem = dfr.real(x), dfr.real(rem)
+        a, b = self.conv1, self.conv2
+        if (self._hip_applies(x, rem)
+                and tuple(rem.shape) == (x.shape[0], a.conv.out_channels, 2 * x.shape[2], 2 * x.shape[3])):
+            y = E.run_deconv2d(a, "c2x", a.conv, a.bn, x, True)
+            if y is not None:
+                PATH_COUNTS["hip"] += 1                        # (one per Conv2x on this path; the stock path counts one per BasicConv)
+                return self._conv2_after_hip_deconv(y, rem)[0]
+        # the reference's own statements, models/submodule.py:149-161
+        x = _stock_basicconv(a, x)
+        if x.shape != rem.shape:
+            x = F.interpolate(x, size=(rem.shape[-2], rem.shape[-1]), mode='bilinear')
+        if self.concat:
+            x = torch.cat((x, rem), 1)
+        else:
+            x = x + rem
+        return _stock_basicconv(b, x)
+
+    def forward_pair(self, xa, rema, xb, remb):
+        """forward(xa, rema), forward(xb, remb) -- FeatUp applies each Conv2x to the left view, then to the right one
+        (models/SemStereo.py:74-84) -- with ONE launch per layer for both views.  The transposed conv gives each view the bits of its
+        own launch (its tile is chosen per layer).  The 3x3 conv chooses its tile from the launch's workgroup count, as the plain 2-D
+        form does, and the block-floating scale is per tile: where two views move a layer onto a larger tile than one view gets, the
+        result differs from the single call's in the last bits (<= 2e-6 on O(1) outputs, tests/test_decoder_gpu.py)."""
+        xa, rema, xb, remb = dfr.real(xa), dfr.real(rema), dfr.real(xb), dfr.real(remb)
+        a = self.conv1
+        if (self._hip_applies(xa, rema, xb, remb) and xa.shape == xb.shape and rema.shape == remb.shape
+                and tuple(rema.shape) == (xa.shape[0], a.conv.out_channels, 2 * xa.shape[2], 2 * xa.shape[3])):
+            B = xa.shape[0]
+            y = E.run_deconv2d(a, "c2x", a.conv, a.bn, xa, True, xb=xb)
+            if y is not None:
+                PATH_COUNTS["hip"] += 1
+                return self._conv2_after_hip_deconv(y[:B], rema, xb=y[B:], remb=remb)
+        return self.forward(xa, rema), self.forward(xb, remb)
+
+
+class FeatUp(nn.Module):
+    """FeatUp (models/SemStereo.py:59-86): four Conv2x up the backbone's pyramid, each applied to the left and to the right view; keys
+    `deconv32_16.*`, `deconv16_8.*`, `deconv8_4.*`, `deconv4_2.*`.  Both views of a layer go through one launch (Conv2x.forward_pair)."""
+
+    def __init__(self):
+        super().__init__()
+        chans = [64, 128, 256, 384, 512]
+        self.deconv32_16 = Conv2x(chans[4], chans[3], deconv=True, concat=True)
+        self.deconv16_8 = Conv2x(chans[3] * 2, chans[2], deconv=True, concat=True)
+        self.deconv8_4 = Conv2x(chans[2] * 2, chans[1], deconv=True, concat=True)
+        self.deconv4_2 = Conv2x(chans[1] * 2, chans[0], deconv=True, concat=True)
+
+    @classmethod
+    def adopt(cls, ref):
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        for name in ("deconv32_16", "deconv16_8", "deconv8_4", "deconv4_2"):
+            sub = getattr(ref, name)
+            setattr(self, name, sub if isinstance(sub, Conv2x) else Conv2x.adopt(sub))
+        self.train(ref.training)
+        return self
+
+    def forward(self, featL, featR=None):
+        x2, x4, x8, x16, x32 = featL
+        y2, y4, y8, y16, y32 = featR
+        x16, y16 = self.deconv32_16.forward_pair(x32, x16, y32, y16)
+        x8, y8 = self.deconv16_8.forward_pair(x16, x8, y16, y8)
+        x4, y4 = self.deconv8_4.forward_pair(x8, x4, y8, y4)
+        x2, y2 = self.deconv4_2.forward_pair(x4, x2, y4, y2)
+        return [x2, x4, x8, x16, x32], [y2, y4, y8, y16, y32]          # (x32 / y32 pass through unchanged, :86)
+
+
+class Spx2(nn.Sequential):
+    """`spx2` (models/SemStereo.py:207): nn.Sequential(nn.ConvTranspose2d(C, 6, 4, 2, 1)) with a bias; keys `0.weight`, `0.bias`.
+    Inference: the transposed kernel with the bias as the epilogue's shift, no ReLU."""
+
+    def __init__(self, in_channels=128, out_channels=6):
+        super().__init__(nn.ConvTranspose2d(in_channels, out_channels, kernel_size=4, stride=2, padding=1))
+
+    @classmethod
+    def adopt(cls, ref):
+        assert len(ref) == 1 and isinstance(ref[0], nn.ConvTranspose2d)
+        self = cls.__new__(cls)
+        nn.Sequential.__init__(self, ref[0])
+        self.train(ref.training)
+        return self
+
+    def forward(self, x):
+        x = dfr.real(x)
+        if isinstance(x, torch.Tensor) and x.is_cuda and _inference(self, x):
+            y = E.run_deconv2d(self, "spx2", self[0], None, x, False)
+            if y is not None:
+                PATH_COUNTS["hip"] += 1
+                return y
+        PATH_COUNTS["torch"] += 1
+        return self[0](x)
 
 
 def __getattr__(name):
