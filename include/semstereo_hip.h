@@ -354,6 +354,36 @@ int ss_deconv2d_bf16s_pair_fwd(const float* in_a, const float* in_b, const void*
  * channel by a power of two, + float[32 ceil(Cout/32)] of the inverse scales:
  * ceil(Cin/8) * ceil(Cout/32) * 16384 + 128 * ceil(Cout/32) bytes, 16-byte aligned. */
 int ss_pack_deconv2d_weights_f16s(const float* w, void* wsplit, int Cin, int Cout, ss_stream_t stream);
+/* Conv2d(Cin, Cout, 1) + per-channel affine + optional ReLU on [B,Cin,npos] maps (npos = H*W) -> out [B,Cout,npos]: the projections
+ * `chal_0 .. chal_4` = nn.Sequential(nn.Conv2d(1x1, bias), nn.BatchNorm2d) (models/SemStereo.py:213-217, called at :258-262), with
+ * the bias and the eval BatchNorm folded into (scale, shift), on the two-term fp16 form of the matrix-core engine with a loop over
+ * Cin: any Cin % 8 == 0 (else SS_ERR_UNSUPPORTED), any Cout >= 1.  A workgroup owns 64 consecutive positions of one element
+ * whatever the batch: an element has the same bits alone, in a batch and in the pair form.  scale / shift may be NULL (1 / 0).
+ * wsplit from ss_pack_conv2d_k1_weights_f16s.  One element's input and output must stay below 2 GiB (SS_ERR_UNSUPPORTED). */
+int ss_conv2d_k1_f16s_fwd(const float* in, const void* wsplit, const float* scale, const float* shift, float* out, int B, int Cin,
+                          long long npos, int Cout, int relu, ss_stream_t stream);
+/* The same layer on TWO input tensors in one launch (chal_1 / chal_2 on the left and on the right view, models/SemStereo.py:259-260,
+ * 264-265): out [2B,Cout,npos], elements 0..B-1 from in_a, B..2B-1 from in_b (both [B,Cin,npos]). */
+int ss_conv2d_k1_f16s_pair_fwd(const float* in_a, const float* in_b, const void* wsplit, const float* scale, const float* shift,
+                               float* out, int B, int Cin, long long npos, int Cout, int relu, ss_stream_t stream);
+/* nn.Conv2d weight [Cout,Cin,1,1] fp32 (models/SemStereo.py:213-217) -> the fragments of ss_conv2d_k1_f16s_fwd:
+ * [ceil(Cin/32)][ceil(Cout/32)][2 K-steps][2 terms][2 channel octets][32 output channels][8] fp16 of w scaled per output channel by
+ * a power of two, + float[32 ceil(Cout/32)] of the inverse scales: ceil(Cin/32) * ceil(Cout/32) * 4096 + 128 * ceil(Cout/32) bytes,
+ * 16-byte aligned. */
+int ss_pack_conv2d_k1_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);
+/* The segmentation head up to its logits (segmenthead.forward, models/submodule.py:42-44: conv1 = BasicConv(Cin, 32, 3x3, padding 1)
+ * = Conv2d(bias=False) + BatchNorm2d + ReLU, :89-116, then conv2 = nn.Conv2d(32, K, 1, bias=True); `head_l` / `head_r`,
+ * models/SemStereo.py:200-201, 254-255) in one pass: the 32-channel map stays in the accumulators.  in [B,Cin,H,W], Cin % 8 == 0;
+ * (scale, shift) the folded eval BatchNorm of conv1 (NULL: 1 / 0); w2 [K,32], bias [K], K <= 8; out [B,K,H,W].  wsplit from
+ * ss_pack_seghead_weights_f16s.  The tile is 8 x 32 positions of one element whatever the batch. */
+int ss_seghead_logits_fwd(const float* in, const void* wsplit, const float* scale, const float* shift, const float* w2,
+                          const float* bias, float* out, int B, int Cin, int H, int W, int K, ss_stream_t stream);
+/* conv1.conv.weight [32,Cin,3,3] fp32 -> the fragments of ss_seghead_logits_fwd: [Cin/8][5 K-steps][2 terms][2 taps][32 channels][8]
+ * fp16 + float[32] inverse scales: Cin/8 * 10240 + 128 bytes, 16-byte aligned. */
+int ss_pack_seghead_weights_f16s(const float* w, void* wsplit, int Cin, ss_stream_t stream);
+/* F.interpolate(in, size=(2H, 2W), mode="bilinear", align_corners=False) of [B,C,H,W] -> [B,C,2H,2W] (segmenthead.forward with
+ * scale_factor 2, models/submodule.py:46-51): weights 0.25 / 0.75, source index clamped at the borders, horizontal pair first. */
+int ss_bilinear_up2_fwd(const float* in, float* out, int B, int C, int H, int W, ss_stream_t stream);
 /* two-term fp16 form of the 2-D weights (nterms = 19 of ss_conv2d_bf16s_fwd; see ss_pack_conv3d_weights_f16s):
  * ceil(Cin/8)*5*2*2*Cout*16 + 4*Cout bytes. */
 int ss_pack_conv2d_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);

@@ -62,6 +62,12 @@ _SIGNATURES = {
     "ss_deconv2d_bf16s_pair_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "ss_pack_deconv2d_weights_f16s": [_P, _P, _I, _I, _P],
     "ss_pack_conv2d_weights_f16s": [_P, _P, _I, _I, _P],
+    "ss_conv2d_k1_f16s_fwd": [_P, _P, _P, _P, _P, _I, _I, ctypes.c_longlong, _I, _I, _P],
+    "ss_conv2d_k1_f16s_pair_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_longlong, _I, _I, _P],
+    "ss_pack_conv2d_k1_weights_f16s": [_P, _P, _I, _I, _P],
+    "ss_seghead_logits_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "ss_pack_seghead_weights_f16s": [_P, _P, _I, _P],
+    "ss_bilinear_up2_fwd": [_P, _P, _I, _I, _I, _I, _P],
     "ss_conv3d_head_bf16s_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "ss_conv3d_head_bf16s_cl_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "ss_conv3d_bf16s_cl_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],

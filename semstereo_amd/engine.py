@@ -550,6 +550,138 @@ def run_deconv2d(owner, key, deconv, bn, x, relu, xb=None):
     return deconv2d_bf16s_hip(x, ws, deconv.out_channels, scale, shift, relu, xb)
 
 
+#: the segmentation heads (`head_l` / `head_r`, models/SemStereo.py:200-201, 254-255) and the `chal_0 .. chal_4` projections
+#: (:213-217, 258-265) on seghead_f16s.hip / proj2d_f16s.hip instead of the stock Conv2d + BatchNorm2d (+ ReLU, F.interpolate) layers.
+#: "auto": on for the f16x3 engine (the kernels have the fp16 form only); SS_HEADS_HIP=0 / 1 forces it.  The twins are swapped in by
+#: `install.accelerate(model, heads=True)`.
+_hd = os.environ.get("SS_HEADS_HIP", "auto")
+HEADS_HIP = "auto" if _hd == "auto" else (_hd != "0")
+
+
+def _heads_hip_on():
+    return CONV_ENGINE == "f16x3" if HEADS_HIP == "auto" else bool(HEADS_HIP)
+
+
+def _is_conv_k1(conv):
+    return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.groups == 1)
+
+
+def pack_conv2d_k1_weight(w):
+    """Conv2d weight [Cout,Cin,1,1] (or [Cout,Cin]) fp32 -> the fragments of ss_conv2d_k1_f16s_fwd (two scaled fp16 terms + the
+    per-channel inverse scales; int16 tensor, 16-B aligned)."""
+    w = w.detach().float().contiguous()
+    _lib.require_device(w)
+    Cout, Cin = w.shape[0], w.shape[1]
+    assert w.numel() == Cout * Cin
+    nmt = (Cout + 31) // 32
+    out = torch.empty(((Cin + 31) // 32) * nmt * 256 * 8 + 2 * 32 * nmt, dtype=torch.int16, device=w.device)
+    with torch.cuda.device(w.device):
+        call("ss_pack_conv2d_k1_weights_f16s", ptr(w), ptr(out), Cout, Cin)
+    return out
+
+
+def conv2d_k1_f16s_hip(x, wsplit, Cout, scale, shift, relu, xb=None):
+    """Conv2d(1x1) + affine + optional ReLU on the two-term fp16 engine; with `xb` both inputs in one launch (-> [2B,Cout,H,W],
+    first B: x's)."""
+    x = x if x.is_contiguous() else x.contiguous()
+    dev = _lib.require_device(x, xb, scale, shift)
+    B, Cin, H, W = x.shape
+    out = torch.empty(((2 if xb is not None else 1) * B, Cout, H, W), dtype=x.dtype, device=x.device)
+    with torch.cuda.device(dev):
+        if xb is not None:
+            xb = xb if xb.is_contiguous() else xb.contiguous()
+            assert xb.shape == x.shape
+            call("ss_conv2d_k1_f16s_pair_fwd", ptr(x), ptr(xb), ptr(wsplit), ptr(scale), ptr(shift), ptr(out), B, Cin, H * W, Cout,
+                 int(relu))
+        else:
+            call("ss_conv2d_k1_f16s_fwd", ptr(x), ptr(wsplit), ptr(scale), ptr(shift), ptr(out), B, Cin, H * W, Cout, int(relu))
+    return out
+
+
+def run_conv2d_k1(owner, key, conv, bn, x, relu, xb=None):
+    """Conv2d(1x1) [+ bias] [+ BN(eval)] [+ ReLU] on the two-term fp16 engine, the bias and the BatchNorm folded into the epilogue:
+    scale = bn.weight / sqrt(var + eps), shift = bn.bias + scale * (conv.bias - mean).  None when it does not apply (another
+    geometry, Cin not a multiple of 8, the f32 / bf16 engines, SS_HEADS_HIP=0, a CPU or non-fp32 tensor)."""
+    if not (_heads_hip_on() and CONV_ENGINE == "f16x3" and _is_conv_k1(conv) and conv.in_channels % 8 == 0
+            and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and x.shape[1] == conv.in_channels and x.numel() > 0
+            and max(conv.in_channels, conv.out_channels) * x.shape[2] * x.shape[3] * 4 < 0x7fffffff
+            and (xb is None or (xb.is_cuda and xb.shape == x.shape and xb.dtype == x.dtype))):
+        return None
+    srcs = [conv.weight] + ([conv.bias] if conv.bias is not None else []) + (
+        [bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+
+    def build():
+        bias = conv.bias.detach().float() if conv.bias is not None else None
+        if bn is not None:
+            sc, sh = fold_bn(bn)
+            if bias is not None:
+                sh = (sh + sc * bias).contiguous()
+        else:
+            sc, sh = None, (bias.contiguous() if bias is not None else None)
+        return pack_conv2d_k1_weight(conv.weight), sc, sh
+    ws, scale, shift = _cache(owner).get(key + "/k1_f16s", srcs, build)
+    return conv2d_k1_f16s_hip(x, ws, conv.out_channels, scale, shift, relu, xb)
+
+
+def pack_seghead_weight(w):
+    """conv1.conv.weight [32,Cin,3,3] fp32 -> the fragments of ss_seghead_logits_fwd (int16 tensor, 16-B aligned)."""
+    w = w.detach().float().contiguous()
+    _lib.require_device(w)
+    Cin = w.shape[1]
+    assert tuple(w.shape) == (32, Cin, 3, 3) and Cin % 8 == 0
+    out = torch.empty((Cin // 8) * 640 * 8 + 2 * 32, dtype=torch.int16, device=w.device)
+    with torch.cuda.device(w.device):
+        call("ss_pack_seghead_weights_f16s", ptr(w), ptr(out), Cin)
+    return out
+
+
+def bilinear_up2_hip(x):
+    """F.interpolate(x, size=(2H, 2W), mode="bilinear", align_corners=False) of a [B,C,H,W] fp32 map."""
+    x = x if x.is_contiguous() else x.contiguous()
+    dev = _lib.require_device(x)
+    B, C, H, W = x.shape
+    out = torch.empty((B, C, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
+    with torch.cuda.device(dev):
+        call("ss_bilinear_up2_fwd", ptr(x), ptr(out), B, C, H, W)
+    return out
+
+
+def seghead_applies(head, x):
+    """The layers and the input ss_seghead_logits_fwd is built for: conv1 = plain 3x3 to 32 channels + BatchNorm + ReLU, conv2 = 1x1
+    with a bias to at most 8 classes, scale_factor 2 or None, Cin a multiple of 8, an fp32 HIP tensor."""
+    a, b = head.conv1, head.conv2
+    return (_heads_hip_on() and CONV_ENGINE == "f16x3" and _is_plain_3x3(a.conv) and a.conv.out_channels == 32
+            and a.conv.in_channels % 8 == 0 and a.use_bn and a.relu and _is_conv_k1(b) and b.bias is not None
+            and b.in_channels == 32 and b.out_channels <= 8 and head.scale_factor in (None, 2)
+            and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and x.shape[1] == a.conv.in_channels and x.numel() > 0 and x.shape[1] * x.shape[2] * x.shape[3] * 4 < 0x7fffffff)
+
+
+def run_seghead(owner, head, x):
+    """segmenthead.forward (models/submodule.py:40-52) in two launches: conv1 + BatchNorm + ReLU + conv2 with the 32-channel map in
+    the accumulators, then the x2 bilinear up-sampling of the logits (skipped for scale_factor None).  None when it does not apply."""
+    if not seghead_applies(head, x):
+        return None
+    a, b = head.conv1, head.conv2
+    srcs = [a.conv.weight, a.bn.weight, a.bn.bias, a.bn.running_mean, a.bn.running_var, b.weight, b.bias]
+
+    def build():
+        sc, sh = fold_bn(a.bn)
+        return (pack_seghead_weight(a.conv.weight), sc, sh, b.weight.detach().float().reshape(b.out_channels, 32).contiguous(),
+                b.bias.detach().float().contiguous())
+    ws, scale, shift, w2, bias = _cache(owner).get("seghead_f16s", srcs, build)
+    x = x if x.is_contiguous() else x.contiguous()
+    dev = _lib.require_device(x, scale, shift, w2, bias)
+    B, Cin, H, W = x.shape
+    logits = torch.empty((B, b.out_channels, H, W), dtype=x.dtype, device=x.device)
+    with torch.cuda.device(dev):
+        call("ss_seghead_logits_fwd", ptr(x), ptr(ws), ptr(scale), ptr(shift), ptr(w2), ptr(bias), ptr(logits), B, Cin, H, W,
+             b.out_channels)
+    return logits if head.scale_factor is None else bilinear_up2_hip(logits)
+
+
 def pack_head_weight_bf16s(w, nterms=6):
     """[1,Cin,3,3,3] fp32 -> split fragments (taps as matrix rows) for ss_conv3d_head_bf16s_fwd: three bf16 terms (nterms 6 / 3)
     or two scaled fp16 terms + the inverse scale (nterms 19)."""
@@ -805,4 +937,4 @@ ATTENTION_FORM = os.environ.get("SS_ATTENTION", "split")      # "split" (3 launc
 
 #: the names tests / tools may SET on this module; `modules.X` forwards reads of them here
 SWITCHES = ("CONV_ENGINE", "DECONV_F16", "DECONV_MIN_WORKGROUPS", "DECONV_BF16S", "CLASSIFIER_CL", "CLASSIFIER_FUSED", "CLASSIFIER_FOLD", "TRAIN_HIP", "SSR_TRAIN_HIP", "LOSS_HIP", "METRICS_HIP", "ATTENTION_FORM",
-            "STEM_LEFT_FUSED", "STEM_PRESPLIT", "STEM_GATHER", "STEM_INPLACE", "HEAD_F16", "CONV2D_HIP", "DECODER_HIP")
+            "STEM_LEFT_FUSED", "STEM_PRESPLIT", "STEM_GATHER", "STEM_INPLACE", "HEAD_F16", "CONV2D_HIP", "DECODER_HIP", "HEADS_HIP")

@@ -103,22 +103,38 @@ _DECODER_SWAPS = {
 }
 
 
-def accelerate(model, fuse_forward=False, decoder=False):
+# ... and of the segmentation heads and the chal_* projections (models/SemStereo.py:200-201, 213-217), swapped by accelerate(heads=True)
+_HEAD_SWAPS = {
+    "head_l": M.segmenthead,
+    "head_r": M.segmenthead,
+    "chal_0": M.ChalProjection,
+    "chal_1": M.ChalProjection,
+    "chal_2": M.ChalProjection,
+    "chal_3": M.ChalProjection,
+    "chal_4": M.ChalProjection,
+}
+
+
+def accelerate(model, fuse_forward=False, decoder=False, heads=False):
     """Replace the hot-path sub-modules of a reference `SemStereo` instance (or of the .module of
     its nn.DataParallel wrapper) by HIP-backed twins that SHARE its parameters; state_dict keys and
     values are unchanged.  With `fuse_forward` the instance's forward is additionally routed through
     `fused_inference_forward` for inference calls.  With `decoder` the 2-D decoder (`feature_up`, `spx32_16` .. `spx4_2`, `spx2`)
     is swapped too: its 4x4 stride-2 transposed convs and concat + 3x3 convs then run on HIP kernels in inference (SS_DECODER_HIP).
+    With `heads` the segmentation heads (`head_l`, `head_r`) and the projections `chal_0` .. `chal_4` are swapped as well (SS_HEADS_HIP); a
+    module without the expected layout -- the WHU variant's pre-activation head -- stays in place.
     Returns the list of swapped attribute names."""
     target = model.module if isinstance(model, nn.DataParallel) else model
     done = []
-    swaps = list(_SWAPS.items()) + (list(_DECODER_SWAPS.items()) if decoder else [])
+    swaps = list(_SWAPS.items()) + (list(_DECODER_SWAPS.items()) if decoder else []) + (list(_HEAD_SWAPS.items()) if heads else [])
     for name, cls in swaps:
         sub = getattr(target, name, None)
         if sub is None or isinstance(sub, cls):
             continue
         before = list(sub.state_dict().keys())
         new = cls.adopt(sub)
+        if new is None:                      # (the twin declines this layout: the module stays)
+            continue
         assert list(new.state_dict().keys()) == before, f"state_dict keys of {name} changed"
         setattr(target, name, new)
         done.append(name)
@@ -197,8 +213,14 @@ def fused_inference_forward(self, left, right, reference_forward=None):
     # label logits are computed whenever the stereo branch runs
     pred_label = self.head_l(fl[0])
     for i, name in enumerate(("chal_0", "chal_1", "chal_2", "chal_3", "chal_4")):            # :258-262
-        fl[i] = getattr(self, name)(fl[i])
-    fr[1], fr[2] = self.chal_1(fr[1]), self.chal_2(fr[2])                                    # :264-265
+        chal = getattr(self, name)
+        if i in (1, 2) and hasattr(chal, "forward_pair"):                                    # (the twin: both views in one launch)
+            fl[i], fr[i] = chal.forward_pair(fl[i], fr[i])
+        else:
+            fl[i] = chal(fl[i])
+    for i, name in ((1, "chal_1"), (2, "chal_2")):                                           # :264-265
+        if not hasattr(getattr(self, name), "forward_pair"):
+            fr[i] = getattr(self, name)(fr[i])
     xspx = self.spx32_16(fl[4], fl[3])                                                       # :267-271
     xspx = self.spx16_8(xspx, fl[2])
     xspx = self.spx8_4(xspx, fl[1])

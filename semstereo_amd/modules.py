@@ -12,6 +12,8 @@ attribute structure and state_dict keys/shapes as the reference, so its checkpoi
   Conv2x             models/submodule.py:119-161      (the 2-D decoder; swapped in by accelerate(decoder=True))
   FeatUp             models/SemStereo.py:59-86
   Spx2               the `spx2` nn.Sequential(ConvTranspose2d), models/SemStereo.py:207
+  segmenthead        models/submodule.py:31-52        (`head_l` / `head_r`; swapped in by accelerate(heads=True))
+  ChalProjection     the `chal_0 .. chal_4` nn.Sequential(Conv2d 1x1, BatchNorm2d), models/SemStereo.py:213-217
 
 The torch layers inside (nn.Conv3d, nn.BatchNorm3d, ...) are parameter containers: in inference
 (`eval()` and no autograd) forward() runs the gfx950 kernels with BatchNorm folded into the
@@ -670,6 +672,8 @@ class SSR_upsample(nn.Module):
         # The reference calls the head twice per forward with the same `spx_pred` / `pred_label` (models/SemStereo.py:311, 324) and in
         # eval returns only the second result (:346): in inference the call hands out a deferred handle (deferred.py), so a result
         # nobody reads -- `pred_att_up` of an eval forward -- is never computed (a dead full-resolution launch per pair before r05).
+        if dfr._is(pred_label, "seghead"):
+            pred_label = pred_label.value()                    # (the segmentation head's handle: its only consumer besides the output)
         if (self.num_classes == 6 and isinstance(weights, torch.Tensor) and isinstance(pred_label, torch.Tensor)
                 and dfr.on(self, *[t for t in (depth_low, weights, pred_label) if isinstance(t, torch.Tensor)])):
             dfr.STATS.setdefault("ssr", {"deferred": 0, "computed": 0})["deferred"] += 1
@@ -929,6 +933,114 @@ class Spx2(nn.Sequential):
                 return y
         PATH_COUNTS["torch"] += 1
         return self[0](x)
+
+
+# --------------------------------------------------------------------------------------
+# the segmentation heads and the chal_* projections (models/submodule.py:31-52, models/SemStereo.py:200-201, 213-217, 254-265)
+# --------------------------------------------------------------------------------------
+
+class segmenthead(nn.Module):
+    """segmenthead (models/submodule.py:31-52): BasicConv(3x3) -> Conv2d(1x1, bias) -> bilinear up-sampling by `scale_factor`; keys
+    `conv1.conv.weight`, `conv1.bn.*`, `conv2.weight`, `conv2.bias`.  Inference with interplanes == 32, at most 8 classes, a channel
+    count that is a multiple of 8 and scale_factor 2 or None runs ss_seghead_logits_fwd (the 32-channel map never leaves the
+    accumulators) and ss_bilinear_up2_fwd; everything else (training, autograd, CPU, float64, another engine, SS_HEADS_HIP=0, other
+    widths or factors) runs the reference's own statements on the stock layers.  Where deferred handles are in use the call hands
+    out a handle, so a result nobody reads -- `pred_label_r` of an eval forward, models/SemStereo.py:255 vs :346 -- is never
+    launched."""
+
+    def __init__(self, inplanes, interplanes, outplanes, scale_factor=None):
+        super().__init__()
+        self.conv1 = BasicConv(inplanes, interplanes, kernel_size=3, padding=1)
+        self.conv2 = nn.Conv2d(interplanes, outplanes, kernel_size=1, padding=0, bias=True)
+        self.scale_factor = scale_factor
+
+    @staticmethod
+    def adoptable(ref):
+        """The `conv1.conv` / `conv1.bn` / `conv2` layout (the WHU variant's pre-activation head, models/submodule_.py:63-86, has
+        `bn1`, `conv1`, `bn2`, `conv2` instead and stays as it is)."""
+        a, b = getattr(ref, "conv1", None), getattr(ref, "conv2", None)
+        return (isinstance(getattr(a, "conv", None), nn.Conv2d) and isinstance(getattr(a, "bn", None), nn.BatchNorm2d)
+                and hasattr(a, "use_bn") and hasattr(a, "relu") and isinstance(b, nn.Conv2d) and hasattr(ref, "scale_factor"))
+
+    @classmethod
+    def adopt(cls, ref):
+        if not cls.adoptable(ref):
+            return None
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.conv1, self.conv2 = ref.conv1, ref.conv2          # (parameter containers: .conv, .bn, .use_bn, .relu are read directly)
+        self.scale_factor = ref.scale_factor
+        self.train(ref.training)
+        return self
+
+    def forward(self, x):
+        if isinstance(x, torch.Tensor) and dfr.on(self, x) and E.seghead_applies(self, x):
+            return dfr.Deferred.call("seghead", self._forward_now, x)
+        return self._forward_now(x)
+
+    def _forward_now(self, x):
+        x = dfr.real(x)
+        if isinstance(x, torch.Tensor) and x.is_cuda and _inference(self, x):
+            y = E.run_seghead(self, self, x)
+            if y is not None:
+                PATH_COUNTS["hip"] += 1
+                return y
+        # the reference's own statements, models/submodule.py:42-52
+        x = _stock_basicconv(self.conv1, x)
+        out = self.conv2(x)
+        if self.scale_factor is not None:
+            height = x.shape[-2] * self.scale_factor
+            width = x.shape[-1] * self.scale_factor
+            out = F.interpolate(out, size=[height, width], mode='bilinear', align_corners=False)
+        return out
+
+
+class ChalProjection(nn.Sequential):
+    """`chal_0 .. chal_4` (models/SemStereo.py:213-217): nn.Sequential(nn.Conv2d(Cin, Cout, 1), nn.BatchNorm2d(Cout)); keys `0.*`,
+    `1.*`.  Inference: ss_conv2d_k1_f16s_fwd with the bias and the BatchNorm folded into the epilogue; `forward_pair` sends the left
+    and the right view (chal_1 / chal_2, :259-260, 264-265) through one launch.  Training, autograd, CPU, float64, another engine,
+    SS_HEADS_HIP=0 or a channel count that is no multiple of 8: the stock layers."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__(nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=1), nn.BatchNorm2d(out_channels))
+
+    @staticmethod
+    def adoptable(ref):
+        return (isinstance(ref, nn.Sequential) and len(ref) == 2 and isinstance(ref[0], nn.Conv2d) and isinstance(ref[1], nn.BatchNorm2d))
+
+    @classmethod
+    def adopt(cls, ref):
+        if not cls.adoptable(ref):
+            return None
+        self = cls.__new__(cls)
+        nn.Sequential.__init__(self, ref[0], ref[1])
+        self.train(ref.training)
+        return self
+
+    def _hip(self, x, xb=None):
+        ts = [x] + ([xb] if xb is not None else [])
+        if all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts) and _inference(self, *ts):
+            return E.run_conv2d_k1(self, "chal", self[0], self[1], x, False, xb=xb)
+        return None
+
+    def forward(self, x):
+        x = dfr.real(x)
+        y = self._hip(x)
+        if y is not None:
+            PATH_COUNTS["hip"] += 1
+            return y
+        PATH_COUNTS["torch"] += 1
+        return self[1](self[0](x))
+
+    def forward_pair(self, xl, xr):
+        """forward(xl), forward(xr) with one launch for both views; every element gets the bits of its own call."""
+        xl, xr = dfr.real(xl), dfr.real(xr)
+        if isinstance(xl, torch.Tensor) and isinstance(xr, torch.Tensor) and xl.shape == xr.shape and xl.dtype == xr.dtype:
+            y = self._hip(xl, xr)
+            if y is not None:
+                PATH_COUNTS["hip"] += 1
+                return y[:xl.shape[0]], y[xl.shape[0]:]
+        return self.forward(xl), self.forward(xr)
 
 
 def __getattr__(name):
