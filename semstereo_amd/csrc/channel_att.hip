@@ -16,26 +16,9 @@
 // output channels) is done by waves 0 and 1, one column tile each.  ~1.3 GFLOP per call: the kernel is bound by the read
 // of the image features (16.8 MB at 1/8 scale, 33.5 MB at 1/4 scale).
 #include "common.h"
+#include "split_bf16.h"
 
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-using f32x2_t = __attribute__((ext_vector_type(2))) float;
-using bf16x2_t = __attribute__((ext_vector_type(2))) __bf16;
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float x0, float x1) {
-    const f32x2_t v = {x0, x1};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-// (x0, x1) -> packed (hi, mid, lo) bf16 pairs with hi + mid + lo == x up to 2^-25 |x|
-__device__ __forceinline__ void split3_pk(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pk_bf16(x0, x1);
-    const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
-    m = cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-    l = cvt_pk_bf16(s0, s1);
-}
 
 // six cross products of (a.hi, a.mid, a.lo) x (b.hi, b.mid, b.lo), smallest first
 __device__ __forceinline__ f32x16 mfma6(const uint4 (&a)[3], const float (&x)[8], f32x16 acc) {

@@ -21,10 +21,10 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "split_bf16.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 template <int KS, int S, int MT, int NT, int TD, int TH, int CIT>
 struct Cfg {

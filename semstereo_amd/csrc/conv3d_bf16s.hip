@@ -38,9 +38,6 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-
 constexpr int KSTEPS = 14;        // ceil(27 taps / 2): the 3-D kernels (BCfg::KSTEPS is the general form)
 // measured-best settings (each was swept on the bench shapes)
 #ifndef SS_IN_STEPS
@@ -72,36 +69,6 @@ constexpr int SS_ROW_PAIR = 1;    // rows whose MFMAs alternate; 2 measured 1 % 
 #ifndef SS_F16_WGS
 #define SS_F16_WGS 2              // workgroups per CU the fp16 form is compiled for (3 = 168 VGPRs: spills, +29 %)
 #endif
-
-__device__ __forceinline__ unsigned bf16_rne(float x) {       // finite inputs
-    unsigned u = __float_as_uint(x);
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ float bf16_up(unsigned b) { return __uint_as_float(b << 16); }
-
-// x -> (hi, mid, lo) bf16 bit patterns with hi + mid + lo == x up to 2^-25 |x|
-__device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l) {
-    h = bf16_rne(x);
-    const float r1 = x - bf16_up(h);
-    m = bf16_rne(r1);
-    const float r2 = r1 - bf16_up(m);
-    l = bf16_rne(r2);
-}
-
-// the same split for two values at once on gfx950's packed converter: v_cvt_pk_bf16_f32 (RNE) gives
-// lo16 = bf16(x0), hi16 = bf16(x1) -- exactly the LDS slot layout -- and the residuals are one v_pk_add_f32
-using bf16x2_t = __attribute__((ext_vector_type(2))) __bf16;
-__device__ __forceinline__ unsigned cvt_pk_bf16(float x0, float x1) {
-    const f32x2_t v = {x0, x1};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ void split3_pk(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pk_bf16(x0, x1);
-    const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
-    m = cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-    l = cvt_pk_bf16(s0, s1);
-}
 
 // KD: kernel depth, 3 (3x3x3) or 1 (3x3 over [B,C,H,W] maps seen as depth-1 volumes: 9 taps, 5 K-steps)
 // WSL: 16-byte LDS slots of a chunk's weight fragments (0: every wave fetches its own)
@@ -419,10 +386,7 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
 #pragma unroll
         for (int q = 0; q < NQ; ++q) rin[q] = load_in(min(q / C::NPOS, nlive - 1), q % C::NPOS);
     }
-    // f16 form: block-floating scale of the staged chunk.  e_cur = biased exponent the accumulators are scaled for
-    // (scale 2^(E_ONE - e)); e_run = that of the running maximum of the tile (monotone: the accumulators only scale DOWN
-    // after the first chunk, so they cannot overflow)
-    int e_cur = E_ONE, e_run = E_MIN;
+    BlockExp bexp;                                              // f16 form: block-floating scale of the staged chunk (split_f16.h)
     // gather form: the prefetched chunk times the attention weights of its positions (models/SemStereo.py:318), rounded to fp32 as
     // the reference's materialised product is
     auto apply_att = [&](int buf) {
@@ -434,10 +398,8 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
         }
     };
     if constexpr (GATHER) apply_att(0);
-    auto publish_max = [&](float m) {                                         // this wave's max(m, |rin|) -> LDS
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) m = fmaxf(m, fabsf(rin[q]));
-        const unsigned wm = wave_max_bits(__float_as_uint(m));
+    auto publish_max = [&](float m) {                                         // this wave's max(m, |rin|) -> LDS (an infinity counts)
+        const unsigned wm = wave_max_bits(__float_as_uint(abs_max<false>(rin, m)));
         if (lane == 0) reinterpret_cast<unsigned*>(&lds[ZSLOT + 1])[wave] = wm;
     };
     if (F16) {
@@ -453,7 +415,7 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
     for (int i = 0; i < MT * NT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    e_cur = E_ONE; e_run = E_MIN;
+    bexp.reset();
     nlive = min(8, Cin);
     for (int ci0 = 0, g0 = 0; ci0 < Cin; ci0 += 8, g0 += KSTEPS) {
         // ---- split + transpose: registers -> [term][position][8 ch] ----
@@ -471,18 +433,14 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
         }
         float in_scale = 1.f;
         if (F16) {
-            const uint4 wm = lds[ZSLOT + 1];
-            const int e_new = max(e_run, (int)(max(max(wm.x, wm.y), max(wm.z, wm.w)) >> 23));     // inf/NaN: 255
-            e_run = e_new;
-            if (e_new != e_cur) {                              // wave-uniform; exact power-of-two rescale
-                const float ratio = __uint_as_float((unsigned)max(127 + e_cur - e_new, 0) << 23);
+            if (bexp.advance(lds[ZSLOT + 1])) {
+                const float ratio = bexp.rescale();
 #pragma unroll
                 for (int i = 0; i < MT * NT; ++i)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[i][r] *= ratio;
-                e_cur = e_new;
             }
-            in_scale = __uint_as_float((unsigned)(127 + E_ONE - e_cur) << 23);
+            in_scale = bexp.in_scale();
         }
         // (a chunk of 8 live channels -- every chunk when Cin % 8 == 0 -- takes the copy of this loop without the
         // per-channel selects: 7 of its 32 VALU instructions per position, ISA count r03)
@@ -667,7 +625,7 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
     if constexpr (HEAD) {
         int ow0, oh0, od0;
         tile_origin(tile, ow0, oh0, od0);
-        const float hunscale = __uint_as_float((unsigned)(127 - E_ONE + e_cur) << 23);
+        const float hunscale = bexp.acc_unscale();
         const float hfloor = (relu & 1) ? 0.f : -__builtin_inff();
         const bool colok = ow0 + l31 < Wo && od0 + dzw < Do;
         // ---- t[tap row][position] of this wave's rows: the accumulators become the B operand as they are ----
@@ -760,7 +718,7 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
     set_outputs(tile);                 // (output addressing is derived here, not kept live through the K loop)
     // ---- epilogue: 32x32 D layout (col = lane & 31 = output column, row = channel, see cbase) ----
     // f16 form: 2^-(activation scale); the per-channel 2^-(weight scale) is stored behind the packed weights
-    const float acc_unscale = __uint_as_float((unsigned)(127 - E_ONE + e_cur) << 23);
+    const float acc_unscale = bexp.acc_unscale();
     const float* obase = out + (size_t)b * Cout * Do * out_plane;
     const __amdgpu_buffer_rsrc_t ores = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(obase), 0, obytes, 0x00020000);
     // the residual: added after the affine, or (res_pre) a partial sum added before it
@@ -902,8 +860,7 @@ __global__ __launch_bounds__(256) void pack_weights_f16s_fused_kernel(const floa
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int e = max((int)(max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])) >> 23), E_MIN);
-        const float u = __uint_as_float((unsigned)(127 - E_ONE + e) << 23);
+        const float u = unscale_for(workgroup_exponent(wmax));
         wunscale[co] = u;
         unscale_s = u;
     }
@@ -921,10 +878,8 @@ __global__ __launch_bounds__(256) void pack_weights_f16s_fused_kernel(const floa
         const int tap = 2 * s + half, ci = blk * 8 + j;
         float x = 0.f;
         if (tap < ktaps && ci < Cin) x = wc[(size_t)ci * ktaps + tap] / u;       // exact: a power of two
-        const _Float16 h = (_Float16)x;
-        const _Float16 l = (_Float16)(x - (float)h);
         const long long i = ((((long long)(blk * KSTEPS + s) * 2 + term) * 2 + half) * Cout + co) * 8 + j;
-        wsplit[i] = __builtin_bit_cast(unsigned short, term == 0 ? h : l);
+        wsplit[i] = split_weight_f16(x, term);
     }
 }
 

@@ -22,24 +22,8 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-using bf16x2_t = __attribute__((ext_vector_type(2))) __bf16;
-using f32x2_t = __attribute__((ext_vector_type(2))) float;
-
 constexpr int TWO = 30;           // output columns per tile (32 lanes - 2 halo columns)
 
-__device__ __forceinline__ unsigned cvt_pk_bf16(float x0, float x1) {       // lo16 = bf16(x0), hi16 = bf16(x1), RNE
-    const f32x2_t v = {x0, x1};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ void split3_pk(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pk_bf16(x0, x1);
-    const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
-    m = cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-    l = cvt_pk_bf16(s0, s1);
-}
 __device__ __forceinline__ float from_lane_below(float v) {   // lane n <- lane n-1
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
 }
@@ -139,8 +123,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_head_bf16s(const float* __restr
 #pragma unroll
                 for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(x[ks][j]));
             const int e = max((int)(wave_max_bits(__float_as_uint(m)) >> 23), E_MIN);       // wave-uniform; inf / NaN: 255
-            const float in_scale = __uint_as_float((unsigned)(127 + E_ONE - e) << 23);
-            row_unscale = __uint_as_float((unsigned)(127 - E_ONE + e) << 23) * w_unscale;     // powers of two: exact
+            const float in_scale = scale_for(e);
+            row_unscale = unscale_for(e) * w_unscale;           // powers of two: exact
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 unsigned bh[4], bl[4];
@@ -234,8 +218,7 @@ __global__ __launch_bounds__(256) void pack_head_weights_f16s_kernel(const float
     const unsigned wm = wave_max_bits(__float_as_uint(m));
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
     __syncthreads();
-    const int e = max((int)(max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])) >> 23), E_MIN);
-    const float unscale = __uint_as_float((unsigned)(127 - E_ONE + e) << 23);
+    const float unscale = unscale_for(workgroup_exponent(wmax));
     if (threadIdx.x == 0) *reinterpret_cast<float*>(wsplit + total) = unscale;
     for (int i = threadIdx.x; i < total; i += 256) {
         const int j = i % 8;
@@ -246,9 +229,7 @@ __global__ __launch_bounds__(256) void pack_head_weights_f16s_kernel(const float
         const int ks = r / 2;
         const int tap = head_row_tap(row), c = ks * 16 + 8 * hk + j;
         const float x = (tap >= 0 && c < Cin) ? w[(size_t)c * 27 + tap] / unscale : 0.f;         // exact: a power of two
-        const _Float16 h = (_Float16)x;
-        const _Float16 l = (_Float16)(x - (float)h);
-        wsplit[i] = __builtin_bit_cast(unsigned short, term == 0 ? h : l);
+        wsplit[i] = split_weight_f16(x, term);
     }
 }
 

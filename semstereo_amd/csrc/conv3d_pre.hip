@@ -21,7 +21,6 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int P_TD = 4, P_TH = 4, P_NT = 4;                  // 4 planes x 4 rows x 32 columns per workgroup; wave = plane
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_pre(const uint4* __restrict__ x
     int cur = 0;
     // the accumulators' scale is the input's block exponent (one per batch element) times the per-channel weight scale
     const int e_in = xexp[b];
-    const float acc_unscale = __uint_as_float((unsigned)(127 - E_ONE + e_in) << 23);
+    const float acc_unscale = unscale_for(e_in);
     __builtin_amdgcn_s_waitcnt(0x0F70);                          // vmcnt(0)
     __syncthreads();
 

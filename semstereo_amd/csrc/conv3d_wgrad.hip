@@ -19,10 +19,10 @@
 #include <algorithm>
 
 #include "common.h"
+#include "split_bf16.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 template <int S>
 __global__ __launch_bounds__(192) void conv3d_wgrad_k3(const float* __restrict__ gout, const float* __restrict__ in,

@@ -34,25 +34,9 @@
 #include <type_traits>
 
 #include "common.h"
+#include "split_bf16.h"
 
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-using f32x2_w = __attribute__((ext_vector_type(2))) float;
-using bf16x2_w = __attribute__((ext_vector_type(2))) __bf16;
-
-__device__ __forceinline__ unsigned cvt_pk_bf16_w(float x0, float x1) {     // lo16 = bf16(x0), hi16 = bf16(x1), RNE
-    const f32x2_w v = {x0, x1};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_w));
-}
-__device__ __forceinline__ void split3_pk_w(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pk_bf16_w(x0, x1);
-    const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
-    m = cvt_pk_bf16_w(r0, r1);
-    const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-    l = cvt_pk_bf16_w(s0, s1);
-}
 
 constexpr int CW = 32;                                    // output positions per chunk (two K-steps of 16)
 template <int S>
@@ -138,19 +122,19 @@ __global__ __launch_bounds__(192, S == 1 ? 3 : 2) void conv3d_wgrad_bf16s(const 
             const int c = 4 * i + csub;
             if constexpr (S == 1) {
                 unsigned h, m, l;
-                split3_pk_w(v[0], v[1], h, m, l);
+                split3_pk(v[0], v[1], h, m, l);
                 unsigned char* p = tile + c * C::RS + 16 + 4 * q;
                 *reinterpret_cast<unsigned*>(p) = h;
                 *reinterpret_cast<unsigned*>(p + C::PLANE) = m;
                 *reinterpret_cast<unsigned*>(p + 2 * C::PLANE) = l;
             } else {
                 unsigned h, m, l;
-                split3_pk_w(v[0], v[2], h, m, l);          // even columns: E[j], E[j + 1]
+                split3_pk(v[0], v[2], h, m, l);          // even columns: E[j], E[j + 1]
                 unsigned char* p = tile + c * C::RS + 4 * q;
                 *reinterpret_cast<unsigned*>(p) = h;
                 *reinterpret_cast<unsigned*>(p + C::PLANE) = m;
                 *reinterpret_cast<unsigned*>(p + 2 * C::PLANE) = l;
-                split3_pk_w(v[1], v[3], h, m, l);          // odd columns: O[j], O[j + 1]
+                split3_pk(v[1], v[3], h, m, l);          // odd columns: O[j], O[j + 1]
                 p = tile + 3 * C::PLANE + c * C::RS + 16 + 4 * q;
                 *reinterpret_cast<unsigned*>(p) = h;
                 *reinterpret_cast<unsigned*>(p + C::PLANE) = m;
@@ -159,7 +143,7 @@ __global__ __launch_bounds__(192, S == 1 ? 3 : 2) void conv3d_wgrad_bf16s(const 
         }
         if (S == 1 || half == 0) {                         // the halo element(s) of channel l31: element 7 (left) / 40 (right) of the row
             unsigned h, m, l;
-            split3_pk_w(rhalo, 0.f, h, m, l);
+            split3_pk(rhalo, 0.f, h, m, l);
             unsigned char* p = tile + (S == 1 ? 0 : 3 * C::PLANE) + l31 * C::RS + ((S == 1 && half) ? 80 : 14);
             *reinterpret_cast<unsigned short*>(p) = (unsigned short)h;
             *reinterpret_cast<unsigned short*>(p + C::PLANE) = (unsigned short)m;
@@ -221,7 +205,7 @@ __global__ __launch_bounds__(192, S == 1 ? 3 : 2) void conv3d_wgrad_bf16s(const 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int w = w0 + 16 * s + 8 * half + 2 * e;
-                    split3_pk_w((WHOLE || w < Wo) ? av[s][2 * e] : 0.f, (WHOLE || w + 1 < Wo) ? av[s][2 * e + 1] : 0.f, h[e], m[e], l[e]);
+                    split3_pk((WHOLE || w < Wo) ? av[s][2 * e] : 0.f, (WHOLE || w + 1 < Wo) ? av[s][2 * e + 1] : 0.f, h[e], m[e], l[e]);
                 }
                 af[s][0] = make_uint4(h[0], h[1], h[2], h[3]);
                 af[s][1] = make_uint4(m[0], m[1], m[2], m[3]);
@@ -385,7 +369,7 @@ __global__ __launch_bounds__(576, 1) void conv3d_wgrad_bf16s_coop(const float* _
                 if (i < i1) {                                // (wave-uniform)
                     const float v0 = (WHOLE || w0 + 2 * q < W) ? rin[k * 2] : 0.f, v1 = (WHOLE || w0 + 2 * q + 1 < W) ? rin[k * 2 + 1] : 0.f;
                     unsigned h, m, l;
-                    split3_pk_w(v0, v1, h, m, l);
+                    split3_pk(v0, v1, h, m, l);
                     unsigned char* p = tile + (4 * i + csub) * C::RS + 16 + 4 * q;
                     *reinterpret_cast<unsigned*>(p) = h;
                     *reinterpret_cast<unsigned*>(p + C::PLANE) = m;
@@ -394,7 +378,7 @@ __global__ __launch_bounds__(576, 1) void conv3d_wgrad_bf16s_coop(const float* _
             }
             if (kh == 2) {                                   // the halo elements of channel l31: element 7 (left) / 40 (right) of the row
                 unsigned h, m, l;
-                split3_pk_w(rhalo, 0.f, h, m, l);
+                split3_pk(rhalo, 0.f, h, m, l);
                 unsigned char* p = tile + l31 * C::RS + (half ? 80 : 14);
                 *reinterpret_cast<unsigned short*>(p) = (unsigned short)h;
                 *reinterpret_cast<unsigned short*>(p + C::PLANE) = (unsigned short)m;
@@ -404,7 +388,7 @@ __global__ __launch_bounds__(576, 1) void conv3d_wgrad_bf16s_coop(const float* _
         if (wave < 8 && t >= oh0 && t < oh1) {
             const float v0 = (WHOLE || w0 + 2 * q < W) ? ra[0] : 0.f, v1 = (WHOLE || w0 + 2 * q + 1 < W) ? ra[1] : 0.f;
             unsigned h, m, l;
-            split3_pk_w(v0, v1, h, m, l);
+            split3_pk(v0, v1, h, m, l);
             unsigned char* p = abuf + (t & 1) * CO_ATILE + (4 * wave + csub) * CO_RSA + 4 * q;
             *reinterpret_cast<unsigned*>(p) = h;
             *reinterpret_cast<unsigned*>(p + 32 * CO_RSA) = m;
@@ -536,12 +520,12 @@ __global__ __launch_bounds__(576, 1) void conv3d_wgrad_bf16s_s2a(const float* __
             for (int e = 0; e < C::NLD; ++e) v[e] = (WHOLE || iw0 + e < W) ? rin[i * C::NLD + e] : 0.f;
             const int c = 4 * i + csub;
             unsigned h, m, l;
-            split3_pk_w(v[0], v[2], h, m, l);              // even columns: E[j], E[j + 1]
+            split3_pk(v[0], v[2], h, m, l);              // even columns: E[j], E[j + 1]
             unsigned char* p = tile + c * C::RS + 4 * q;
             *reinterpret_cast<unsigned*>(p) = h;
             *reinterpret_cast<unsigned*>(p + C::PLANE) = m;
             *reinterpret_cast<unsigned*>(p + 2 * C::PLANE) = l;
-            split3_pk_w(v[1], v[3], h, m, l);              // odd columns: O[j], O[j + 1]
+            split3_pk(v[1], v[3], h, m, l);              // odd columns: O[j], O[j + 1]
             p = tile + 3 * C::PLANE + c * C::RS + 16 + 4 * q;
             *reinterpret_cast<unsigned*>(p) = h;
             *reinterpret_cast<unsigned*>(p + C::PLANE) = m;
@@ -549,7 +533,7 @@ __global__ __launch_bounds__(576, 1) void conv3d_wgrad_bf16s_s2a(const float* __
         }
         if (half == 0) {
             unsigned h, m, l;
-            split3_pk_w(rhalo, 0.f, h, m, l);
+            split3_pk(rhalo, 0.f, h, m, l);
             unsigned char* p = tile + 3 * C::PLANE + l31 * C::RS + 14;
             *reinterpret_cast<unsigned short*>(p) = (unsigned short)h;
             *reinterpret_cast<unsigned short*>(p + C::PLANE) = (unsigned short)m;
@@ -587,7 +571,7 @@ __global__ __launch_bounds__(576, 1) void conv3d_wgrad_bf16s_s2a(const float* __
         if (wave < 8) {
             const float v0 = (whole || w0 + 2 * q < Wo) ? ra[0] : 0.f, v1 = (whole || w0 + 2 * q + 1 < Wo) ? ra[1] : 0.f;
             unsigned h, m, l;
-            split3_pk_w(v0, v1, h, m, l);
+            split3_pk(v0, v1, h, m, l);
             unsigned char* p = abuf + par * CO_ATILE + (4 * wave + csub) * CO_RSA + 4 * q;
             *reinterpret_cast<unsigned*>(p) = h;
             *reinterpret_cast<unsigned*>(p + 32 * CO_RSA) = m;
@@ -690,7 +674,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_head_bf16s(const float* __re
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int w = w0 + 16 * s + 8 * half + 2 * e;
-                split3_pk_w(w < W ? av[s][2 * e] : 0.f, w + 1 < W ? av[s][2 * e + 1] : 0.f, h[e], m[e], l[e]);
+                split3_pk(w < W ? av[s][2 * e] : 0.f, w + 1 < W ? av[s][2 * e + 1] : 0.f, h[e], m[e], l[e]);
             }
             af[s][0] = make_uint4(h[0], h[1], h[2], h[3]); af[s][1] = make_uint4(m[0], m[1], m[2], m[3]); af[s][2] = make_uint4(l[0], l[1], l[2], l[3]);
         }
@@ -702,7 +686,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_head_bf16s(const float* __re
             unsigned h[4], m[4], l[4];
             const float* gp = &gt[trow][16 * s + 8 * half + 2 - kw];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) split3_pk_w(tap_ok ? gp[2 * e] : 0.f, tap_ok ? gp[2 * e + 1] : 0.f, h[e], m[e], l[e]);
+            for (int e = 0; e < 4; ++e) split3_pk(tap_ok ? gp[2 * e] : 0.f, tap_ok ? gp[2 * e + 1] : 0.f, h[e], m[e], l[e]);
             bf[0] = make_uint4(h[0], h[1], h[2], h[3]); bf[1] = make_uint4(m[0], m[1], m[2], m[3]); bf[2] = make_uint4(l[0], l[1], l[2], l[3]);
             constexpr int pa[6] = {1, 0, 2, 0, 1, 0}, pb[6] = {1, 2, 0, 1, 0, 0};
 #pragma unroll

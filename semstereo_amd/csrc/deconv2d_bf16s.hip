@@ -25,9 +25,6 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-
 template <int NT>
 struct DCfg {
     static constexpr int TH = 4 * NT, IH = TH + 2, IW = 34;
@@ -76,14 +73,8 @@ __global__ __launch_bounds__(256, 2) void deconv2d_f16s(const float* __restrict_
                 rin[c * C::NPOS + i] = (ch < Cin && poff[i] >= 0) ? inb[(size_t)ch * plane + poff[i]] : 0.f;
         }
     };
-    auto publish_max = [&]() {                                 // this wave's max |rin| -> LDS
-        float m = 0.f;
-#pragma unroll
-        for (int q = 0; q < 8 * C::NPOS; ++q) {                // (an infinity -- like a NaN, which fmaxf drops -- does not set the tile's
-            const float ax = fabsf(rin[q]);                    // scale: it poisons its own receptive field and nothing else)
-            m = fmaxf(m, ax == __builtin_inff() ? 0.f : ax);
-        }
-        const unsigned wm = wave_max_bits(__float_as_uint(m));
+    auto publish_max = [&]() {                                 // this wave's max |rin| -> LDS (an infinity poisons its own receptive field only)
+        const unsigned wm = wave_max_bits(__float_as_uint(abs_max<true>(rin, 0.f)));
         if (lane == 0) reinterpret_cast<unsigned*>(&lds[MSLOT])[wave] = wm;
     };
 
@@ -98,24 +89,18 @@ __global__ __launch_bounds__(256, 2) void deconv2d_f16s(const float* __restrict_
     fetch(0);
     publish_max();
     __syncthreads();
-    // block-floating scale of the staged chunk (split_f16.h): e_cur = biased exponent the accumulators are scaled for, e_run = that
-    // of the tile's running maximum (monotone: the accumulators only scale down after the first chunk)
-    int e_cur = E_ONE, e_run = E_MIN;
+    BlockExp bexp;                                             // block-floating scale of the staged chunk (split_f16.h)
     for (int chunk = 0; chunk < nchunks; ++chunk) {
-        const uint4 wm = lds[MSLOT];
-        const int e_new = max(e_run, (int)(max(max(wm.x, wm.y), max(wm.z, wm.w)) >> 23));
-        e_run = e_new;
-        if (e_new != e_cur) {                                  // workgroup-uniform; an exact power-of-two rescale
-            const float ratio = __uint_as_float((unsigned)max(127 + e_cur - e_new, 0) << 23);
+        if (bexp.advance(lds[MSLOT])) {
+            const float ratio = bexp.rescale();
 #pragma unroll
             for (int i = 0; i < NT; ++i)
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[i][k][r] *= ratio;
-            e_cur = e_new;
         }
-        const float in_scale = __uint_as_float((unsigned)(127 + E_ONE - e_cur) << 23);
+        const float in_scale = bexp.in_scale();
         // ---- split + transpose: registers -> [term][position][8 ch] ----
 #pragma unroll
         for (int i = 0; i < C::NPOS; ++i) {
@@ -157,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void deconv2d_f16s(const float* __restrict_
     }
 
     // ---- epilogue: 32x32 D layout (column = lane & 31 = input column, register r = channel (r & 3) + 8 (r >> 2) + 4 half) ----
-    const float acc_unscale = __uint_as_float((unsigned)(127 - E_ONE + e_cur) << 23);
+    const float acc_unscale = bexp.acc_unscale();
     const int x = x0 + l31;
     const int Ho = 2 * H, Wo = 2 * W;
 #pragma unroll
@@ -201,8 +186,7 @@ __global__ __launch_bounds__(256) void pack_deconv2d_f16s_kernel(const float* __
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int e = max((int)(max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])) >> 23), E_MIN);
-        const float u = __uint_as_float((unsigned)(127 - E_ONE + e) << 23);
+        const float u = unscale_for(workgroup_exponent(wmax));
         wunscale[co] = u;
         unscale_s = u;
     }
@@ -221,10 +205,8 @@ __global__ __launch_bounds__(256) void pack_deconv2d_f16s_kernel(const float* __
         const int py = cls >> 1, px = cls & 1, ci = chunk * 8 + j;
         float x = 0.f;
         if (live && ci < Cin) x = w[((size_t)ci * Cout + co) * 16 + (3 - py - 2 * dy) * 4 + (3 - px - 2 * dx)] / u;      // exact: a power of two
-        const _Float16 h = (_Float16)x;
-        const _Float16 l = (_Float16)(x - (float)h);
         const size_t i = ((((size_t)chunk * nct + ct) * 16 + (cls * 2 + dy) * 2 + term) * 64 + dx * 32 + cl) * 8 + j;
-        wsplit[i] = __builtin_bit_cast(unsigned short, term == 0 ? h : l);
+        wsplit[i] = split_weight_f16(x, term);
     }
 }
 

@@ -17,10 +17,10 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "split_bf16.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 template <int TD, int TH, int CIT>
 struct DCfg {

@@ -18,25 +18,9 @@
 #include "common.h"
 #include "split_f16.h"
 
-
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-using bf16x2_t = __attribute__((ext_vector_type(2))) __bf16;
 using ss_u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float x0, float x1) {       // lo16 = bf16(x0), hi16 = bf16(x1), RNE
-    const f32x2_t v = {x0, x1};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ void split3_pk(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pk_bf16(x0, x1);
-    const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
-    m = cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-    l = cvt_pk_bf16(s0, s1);
-}
 
 // taps (kd*9 + kh*3 + kw) grouped by input offset o = (kd==0)*4 + (kh==0)*2 + (kw==0); class = (kd!=1)*4 + (kh!=1)*2 + (kw!=1)
 __host__ __device__ constexpr int tap_of(int s) {
@@ -340,12 +324,9 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
             }
         }
     }
-    // fp16 form: block-floating scale of the staged chunk (see conv3d_bf16s.hip)
-    int e_cur = E_ONE, e_run = E_MIN;
-    auto publish_max = [&](float m) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) m = fmaxf(m, fabsf(rin[q]));
-        const unsigned wm = wave_max_bits(__float_as_uint(m));
+    BlockExp bexp;                                             // fp16 form: block-floating scale of the staged chunk (split_f16.h)
+    auto publish_max = [&](float m0) {                         // this wave's max(m0, |rin|) -> LDS (an infinity counts)
+        const unsigned wm = wave_max_bits(__float_as_uint(abs_max<false>(rin, m0)));
         if (lane == 0) reinterpret_cast<unsigned*>(&lds[MSLOT])[wave] = wm;
     };
     if (F16) {
@@ -355,7 +336,7 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
             for (int p = 0; p < NA; ++p)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) m0 = fmaxf(m0, fabsf(acc[p][r]));
-            m0 *= __uint_as_float((unsigned)(127 - E_INIT_SHIFT) << 23);
+            m0 *= pow2_biased(127 - E_INIT_SHIFT);
         }
         publish_max(m0);
         __syncthreads();
@@ -381,18 +362,14 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
         }
         float in_scale = 1.f;
         if (F16) {
-            const uint4 wm = lds[MSLOT];
-            const int e_new = max(e_run, (int)(max(max(wm.x, wm.y), max(wm.z, wm.w)) >> 23));
-            e_run = e_new;
-            if (e_new != e_cur) {                              // wave-uniform; exact power-of-two rescale
-                const float ratio = __uint_as_float((unsigned)max(127 + e_cur - e_new, 0) << 23);
+            if (bexp.advance(lds[MSLOT])) {
+                const float ratio = bexp.rescale();
 #pragma unroll
                 for (int p = 0; p < NA; ++p)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[p][r] *= ratio;
-                e_cur = e_new;
             }
-            in_scale = __uint_as_float((unsigned)(127 + E_ONE - e_cur) << 23);
+            in_scale = bexp.in_scale();
         }
 #pragma unroll
         for (int i = 0; i < C::NPOS; ++i) {
@@ -507,7 +484,7 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
         __syncthreads();
     }
     if (F16) {          // back to plain values: 2^-(activation scale) x the channel's 2^-(weight scale), exact
-        const float au = __uint_as_float((unsigned)(127 - E_ONE + e_cur) << 23);
+        const float au = bexp.acc_unscale();
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float un = au * aff[32 + (r & 3) + 8 * (r >> 2) + 4 * half];
@@ -605,10 +582,7 @@ __global__ __launch_bounds__(256) void deconv_weight_unscale_f16s_kernel(const f
     const unsigned wm = wave_max_bits(__float_as_uint(m));
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const int e = max((int)(max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])) >> 23), E_MIN);
-        wunscale[blockIdx.x] = __uint_as_float((unsigned)(127 - E_ONE + e) << 23);
-    }
+    if (threadIdx.x == 0) wunscale[blockIdx.x] = unscale_for(workgroup_exponent(wmax));
 }
 // pass 2: -> [ceil(Cin/16)][27 K-steps][2 terms][2 channel halves][Cout][8] fp16 of w / wunscale[co]
 __global__ void pack_deconv_weights_f16s_kernel(const float* __restrict__ wpack, unsigned short* __restrict__ wsplit,
@@ -624,9 +598,7 @@ __global__ void pack_deconv_weights_f16s_kernel(const float* __restrict__ wpack,
     const int chunk = (int)(r / 27);
     const int ci = chunk * 16 + hf * 8 + j;
     const float x = (ci < Cin) ? wpack[((size_t)ci * 27 + tap_of(s)) * Cout + co] / wunscale[co] : 0.f;
-    const _Float16 h = (_Float16)x;
-    const _Float16 l = (_Float16)(x - (float)h);
-    wsplit[i] = __builtin_bit_cast(unsigned short, term == 0 ? h : l);
+    wsplit[i] = split_weight_f16(x, term);
 }
 
 template <int TD, int TH, int NTERMS, bool HAS_SKIP, bool SPLIT = false, bool ACCB = false, bool STREAM = false>

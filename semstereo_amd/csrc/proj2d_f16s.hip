@@ -22,9 +22,6 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-
 constexpr int P_TILE = 64;                                     // positions per workgroup
 constexpr int P_CHUNK = 32;                                    // channels per staged chunk (two K-steps)
 constexpr int P_ACT = 2 * 4 * P_TILE;                          // 16-byte slots: two terms x four octets x positions
@@ -51,14 +48,8 @@ __global__ __launch_bounds__(256, 2) void proj2d_f16s(const float* __restrict__ 
 #pragma unroll
         for (int c = 0; c < 8; ++c) rin[c] = (pvalid && ch0 + c < Cin) ? inb[(size_t)(ch0 + c) * npos + pmine] : 0.f;
     };
-    auto publish_max = [&]() {                                 // this wave's max |rin| -> LDS
-        float m = 0.f;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {                          // (an infinity -- like a NaN, which fmaxf drops -- does not set the tile's
-            const float ax = fabsf(rin[q]);                    // scale: it poisons its own position and nothing else)
-            m = fmaxf(m, ax == __builtin_inff() ? 0.f : ax);
-        }
-        const unsigned wm = wave_max_bits(__float_as_uint(m));
+    auto publish_max = [&]() {                                 // this wave's max |rin| -> LDS (an infinity poisons its own position only)
+        const unsigned wm = wave_max_bits(__float_as_uint(abs_max<true>(rin, 0.f)));
         if (lane == 0) reinterpret_cast<unsigned*>(&lds[P_ACT])[wave] = wm;
     };
 
@@ -83,9 +74,7 @@ __global__ __launch_bounds__(256, 2) void proj2d_f16s(const float* __restrict__ 
     fetch(0);
     publish_max();
     __syncthreads();
-    // block-floating scale of the staged chunk (split_f16.h): e_cur = biased exponent the accumulators are scaled for, e_run = that
-    // of the tile's running maximum (monotone: the accumulators only scale down after the first chunk)
-    int e_cur = E_ONE, e_run = E_MIN;
+    BlockExp bexp;                                             // block-floating scale of the staged chunk (split_f16.h)
     for (int chunk = 0; chunk < nchunks; ++chunk) {
         // this chunk's weight fragments of this wave's tiles: [chunk][tile][K-step][term][lane]
         u32x4 wf[MT][4];
@@ -95,20 +84,16 @@ __global__ __launch_bounds__(256, 2) void proj2d_f16s(const float* __restrict__ 
 #pragma unroll
             for (int q = 0; q < 4; ++q) wf[m][q] = wc[q * 64];
         }
-        const uint4 wm = lds[P_ACT];
-        const int e_new = max(e_run, (int)(max(max(wm.x, wm.y), max(wm.z, wm.w)) >> 23));
-        e_run = e_new;
-        if (e_new != e_cur) {                                  // workgroup-uniform; an exact power-of-two rescale
-            const float ratio = __uint_as_float((unsigned)max(127 + e_cur - e_new, 0) << 23);
+        if (bexp.advance(lds[P_ACT])) {
+            const float ratio = bexp.rescale();
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int n = 0; n < 2; ++n)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[m][n][r] *= ratio;
-            e_cur = e_new;
         }
-        const float in_scale = __uint_as_float((unsigned)(127 + E_ONE - e_cur) << 23);
+        const float in_scale = bexp.in_scale();
         // ---- split: registers -> [term][octet][position][8 ch] ----
         {
             unsigned hh[4], ll[4];
@@ -148,7 +133,7 @@ __global__ __launch_bounds__(256, 2) void proj2d_f16s(const float* __restrict__ 
     }
 
     // ---- epilogue: 32x32 D layout (column = lane & 31 = position, register r = channel (r & 3) + 8 (r >> 2) + 4 half) ----
-    const float acc_unscale = __uint_as_float((unsigned)(127 - E_ONE + e_cur) << 23);
+    const float acc_unscale = bexp.acc_unscale();
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
         if (!live[m]) continue;
@@ -187,8 +172,7 @@ __global__ __launch_bounds__(256) void pack_proj2d_f16s_kernel(const float* __re
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int e = max((int)(max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])) >> 23), E_MIN);
-        const float u = __uint_as_float((unsigned)(127 - E_ONE + e) << 23);
+        const float u = unscale_for(workgroup_exponent(wmax));
         wunscale[co] = u;
         unscale_s = u;
     }
@@ -206,10 +190,8 @@ __global__ __launch_bounds__(256) void pack_proj2d_f16s_kernel(const float* __re
         const int ci = chunk * P_CHUNK + ks * 16 + oct * 8 + j;
         float x = 0.f;
         if (live && ci < Cin) x = w[(size_t)co * Cin + ci] / u;                 // exact: a power of two
-        const _Float16 h = (_Float16)x;
-        const _Float16 l = (_Float16)(x - (float)h);
         const size_t i = ((((size_t)chunk * nmt + t) * 4 + ks * 2 + term) * 64 + oct * 32 + cl) * 8 + j;
-        wsplit[i] = __builtin_bit_cast(unsigned short, term == 0 ? h : l);
+        wsplit[i] = split_weight_f16(x, term);
     }
 }
 

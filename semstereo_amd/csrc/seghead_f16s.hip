@@ -25,9 +25,6 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-
 constexpr int H_NT = 2, H_TH = 4 * H_NT, H_IH = H_TH + 2, H_IW = 34;
 constexpr int H_CS = H_IH * H_IW;                              // halo positions
 constexpr int H_NPOS = (H_CS + 255) / 256;                     // positions per thread
@@ -75,14 +72,8 @@ __global__ __launch_bounds__(256, 2) void seghead_logits_f16s(const float* __res
             for (int i = 0; i < H_NPOS; ++i) rin[c * H_NPOS + i] = poff[i] >= 0 ? inb[(size_t)ch * plane + poff[i]] : 0.f;
         }
     };
-    auto publish_max = [&]() {                                 // this wave's max |rin| -> LDS
-        float m = 0.f;
-#pragma unroll
-        for (int q = 0; q < 8 * H_NPOS; ++q) {                 // (an infinity -- like a NaN, which fmaxf drops -- does not set the tile's
-            const float ax = fabsf(rin[q]);                    // scale: it poisons its own receptive field and nothing else)
-            m = fmaxf(m, ax == __builtin_inff() ? 0.f : ax);
-        }
-        const unsigned wm = wave_max_bits(__float_as_uint(m));
+    auto publish_max = [&]() {                                 // this wave's max |rin| -> LDS (an infinity poisons its own receptive field only)
+        const unsigned wm = wave_max_bits(__float_as_uint(abs_max<true>(rin, 0.f)));
         if (lane == 0) reinterpret_cast<unsigned*>(&lds[MSLOT])[wave] = wm;
     };
 
@@ -103,22 +94,16 @@ __global__ __launch_bounds__(256, 2) void seghead_logits_f16s(const float* __res
     fetch(0);
     publish_max();
     __syncthreads();
-    // block-floating scale of the staged chunk (split_f16.h): e_cur = biased exponent the accumulators are scaled for, e_run = that
-    // of the tile's running maximum (monotone: the accumulators only scale down after the first chunk)
-    int e_cur = E_ONE, e_run = E_MIN;
+    BlockExp bexp;                                             // block-floating scale of the staged chunk (split_f16.h)
     for (int chunk = 0; chunk < nchunks; ++chunk) {
-        const uint4 wm = lds[MSLOT];
-        const int e_new = max(e_run, (int)(max(max(wm.x, wm.y), max(wm.z, wm.w)) >> 23));
-        e_run = e_new;
-        if (e_new != e_cur) {                                  // workgroup-uniform; an exact power-of-two rescale
-            const float ratio = __uint_as_float((unsigned)max(127 + e_cur - e_new, 0) << 23);
+        if (bexp.advance(lds[MSLOT])) {
+            const float ratio = bexp.rescale();
 #pragma unroll
             for (int i = 0; i < H_NT; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][r] *= ratio;
-            e_cur = e_new;
         }
-        const float in_scale = __uint_as_float((unsigned)(127 + E_ONE - e_cur) << 23);
+        const float in_scale = bexp.in_scale();
         // ---- split + transpose: registers -> [term][position][8 ch] ----
 #pragma unroll
         for (int i = 0; i < H_NPOS; ++i) {
@@ -157,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void seghead_logits_f16s(const float* __res
     }
 
     // ---- epilogue: 32x32 D layout (column = lane & 31 = input column, register r = channel (r & 3) + 8 (r >> 2) + 4 half) ----
-    const float acc_unscale = __uint_as_float((unsigned)(127 - E_ONE + e_cur) << 23);
+    const float acc_unscale = bexp.acc_unscale();
     const int x = x0 + l31;
     float part[H_NT][H_KMAX];
 #pragma unroll
@@ -203,8 +188,7 @@ __global__ __launch_bounds__(256) void pack_seghead_f16s_kernel(const float* __r
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int e = max((int)(max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])) >> 23), E_MIN);
-        const float u = __uint_as_float((unsigned)(127 - E_ONE + e) << 23);
+        const float u = unscale_for(workgroup_exponent(wmax));
         wunscale[co] = u;
         unscale_s = u;
     }
@@ -221,10 +205,8 @@ __global__ __launch_bounds__(256) void pack_seghead_f16s_kernel(const float* __r
         const int tap = 2 * ks + hf, ci = chunk * 8 + j;
         float x = 0.f;
         if (tap < 9) x = w[((size_t)co * Cin + ci) * 9 + tap] / u;             // exact: a power of two
-        const _Float16 h = (_Float16)x;
-        const _Float16 l = (_Float16)(x - (float)h);
         const size_t i = ((((size_t)chunk * 5 + ks) * 2 + term) * 64 + hf * 32 + co) * 8 + j;
-        wsplit[i] = __builtin_bit_cast(unsigned short, term == 0 ? h : l);
+        wsplit[i] = split_weight_f16(x, term);
     }
 }
 

@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "split_bf16.h"
 
 namespace {
 
@@ -113,23 +114,6 @@ extern "C" int ss_stem_left_fwd(const float* q, const float* att, float* out, in
 // [pair][64][C]), parked in LDS, and consumed by the 27 multiply-adds per output as above.  Saves the 226 MB write and
 // ~300 MB read of Q.
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-using bf16x2_t = __attribute__((ext_vector_type(2))) __bf16;
-using f32x2_t = __attribute__((ext_vector_type(2))) float;
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float x0, float x1) {
-    const f32x2_t v = {x0, x1};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ void split3_pk(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pk_bf16(x0, x1);
-    const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
-    m = cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-    l = cvt_pk_bf16(s0, s1);
-}
 
 constexpr int FTH = 4, FTW = 32;                    // output tile
 constexpr int HH = FTH + 2, HW = FTW + 2;           // halo tile 6 x 34

@@ -19,7 +19,6 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int HD = 8;      // head dim (C / heads)
 constexpr int HG = 4;      // heads per group -> 32 channels = one MFMA M-tile per q / k / v
@@ -312,9 +311,9 @@ __global__ __launch_bounds__(256) void window_attention_core(const float* __rest
 
     const float scale = 0.35355339059327379f;    // 8 ** -0.5
     // block exponent of V (see the P V product below): max -> [2^14, 2^15); a non-finite V makes the scale non-finite
-    const int e_v = max((int)(max(max(vmax_w[0], vmax_w[1]), max(vmax_w[2], vmax_w[3])) >> 23), E_MIN);
-    const float v_scale = __uint_as_float((unsigned)(127 + E_ONE - e_v) << 23);
-    const float pv_unscale = __uint_as_float((unsigned)(127 - E_ONE + e_v) << 23) * (1.0f / 16384.0f);
+    const int e_v = workgroup_exponent(vmax_w);
+    const float v_scale = scale_for(e_v);
+    const float pv_unscale = unscale_for(e_v) * (1.0f / 16384.0f);
     // V -> two scaled fp16 terms, IN PLACE and in the order the P V product reads it: the 16 tokens of a K-step (64 bytes of a
     // V row) become [half 0: hi, lo][half 1: hi, lo], 8 fp16 each, lane half h holding tokens {4 h .. +3, 8 + 4 h .. +3} of
     // the step.  Once per workgroup instead of once per (head, query tile) unit.

@@ -143,6 +143,21 @@ def fold_bn(bn):
     return scale.float().contiguous(), shift.float().contiguous()
 
 
+def _packed_affine(owner, key, conv, bn, pack, bias=False):
+    """(pack(conv.weight), scale, shift), cached on `owner` under `key`: a layer's packed weight and its epilogue affine -- the eval
+    BatchNorm folded (fold_bn; None, None without one) and, with bias=True, the layer's bias too: shift + scale * bias under a
+    BatchNorm, the bias alone as the shift without."""
+    b = conv.bias if bias else None
+    srcs = [conv.weight] + ([b] if b is not None else []) + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+
+    def build():
+        sc, sh = fold_bn(bn) if bn is not None else (None, None)
+        if b is not None:
+            sh = (b.detach().float() if bn is None else sh + sc * b.detach().float()).contiguous()
+        return pack(conv.weight), sc, sh
+    return _cache(owner).get(key, srcs, build)
+
+
 def pack_conv_weight(w, transposed=False):
     """[Cout,Cin,k,k,k] (or ConvTranspose3d's [Cin,Cout,k,k,k]) -> [Cin][k^3][Cout] on the device."""
     w = w.detach().float().contiguous()
@@ -422,12 +437,7 @@ def run_conv2d(owner, key, conv, bn, x, relu):
     if not (_conv2d_hip_on() and CONV_ENGINE != "f32" and _is_plain_3x3(conv) and x.is_cuda):
         return None
     nterms = _tiled_nterms()
-    srcs = [conv.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-
-    def build():
-        sc, sh = fold_bn(bn) if bn is not None else (None, None)
-        return pack_conv2d_weight_bf16s(conv.weight, nterms), sc, sh
-    ws, scale, shift = _cache(owner).get(key + "/2d_" + CONV_ENGINE, srcs, build)
+    ws, scale, shift = _packed_affine(owner, key + "/2d_" + CONV_ENGINE, conv, bn, lambda w: pack_conv2d_weight_bf16s(w, nterms))
     return conv2d_bf16s_hip(x, ws, conv.out_channels, scale, shift, relu, nterms)
 
 
@@ -437,12 +447,7 @@ def run_conv2d_pair(owner, key, conv, bn, xa, xb, relu):
             and xa.shape == xb.shape and xa.dtype == xb.dtype == torch.float32):
         return None
     nterms = _tiled_nterms()
-    srcs = [conv.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-
-    def build():
-        sc, sh = fold_bn(bn) if bn is not None else (None, None)
-        return pack_conv2d_weight_bf16s(conv.weight, nterms), sc, sh
-    ws, scale, shift = _cache(owner).get(key + "/2d_" + CONV_ENGINE, srcs, build)
+    ws, scale, shift = _packed_affine(owner, key + "/2d_" + CONV_ENGINE, conv, bn, lambda w: pack_conv2d_weight_bf16s(w, nterms))
     xa, xb = xa.contiguous(), xb.contiguous()
     dev = _lib.require_device(xa, xb, scale, shift)
     B, Cin, H, W = xa.shape
@@ -465,12 +470,7 @@ def run_conv2d_cat(owner, key, conv, bn, xa, rema, relu, xb=None, remb=None):
             and (xb is None or (xb.shape == xa.shape and remb.shape == rema.shape))):
         return None
     nterms = _tiled_nterms()
-    srcs = [conv.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-
-    def build():
-        sc, sh = fold_bn(bn) if bn is not None else (None, None)
-        return pack_conv2d_weight_bf16s(conv.weight, nterms), sc, sh
-    ws, scale, shift = _cache(owner).get(key + "/2d_" + CONV_ENGINE, srcs, build)
+    ws, scale, shift = _packed_affine(owner, key + "/2d_" + CONV_ENGINE, conv, bn, lambda w: pack_conv2d_weight_bf16s(w, nterms))
     ts = [t.contiguous() for t in ts]
     dev = _lib.require_device(*ts, scale, shift)
     B, _, H, W = xa.shape
@@ -537,16 +537,7 @@ def run_deconv2d(owner, key, deconv, bn, x, relu, xb=None):
             and x.dim() == 4 and x.shape[1] == deconv.in_channels and (bn is None or deconv.bias is None)
             and (xb is None or (xb.is_cuda and xb.shape == x.shape and xb.dtype == x.dtype))):
         return None
-    srcs = [deconv.weight] + ([deconv.bias] if deconv.bias is not None else []) + (
-        [bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-
-    def build():
-        if bn is not None:
-            sc, sh = fold_bn(bn)
-        else:
-            sc, sh = None, (deconv.bias.detach().float().contiguous() if deconv.bias is not None else None)
-        return pack_deconv2d_weight(deconv.weight), sc, sh
-    ws, scale, shift = _cache(owner).get(key + "/dc2d_f16s", srcs, build)
+    ws, scale, shift = _packed_affine(owner, key + "/dc2d_f16s", deconv, bn, pack_deconv2d_weight, bias=True)
     return deconv2d_bf16s_hip(x, ws, deconv.out_channels, scale, shift, relu, xb)
 
 
@@ -609,19 +600,7 @@ def run_conv2d_k1(owner, key, conv, bn, x, relu, xb=None):
             and max(conv.in_channels, conv.out_channels) * x.shape[2] * x.shape[3] * 4 < 0x7fffffff
             and (xb is None or (xb.is_cuda and xb.shape == x.shape and xb.dtype == x.dtype))):
         return None
-    srcs = [conv.weight] + ([conv.bias] if conv.bias is not None else []) + (
-        [bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-
-    def build():
-        bias = conv.bias.detach().float() if conv.bias is not None else None
-        if bn is not None:
-            sc, sh = fold_bn(bn)
-            if bias is not None:
-                sh = (sh + sc * bias).contiguous()
-        else:
-            sc, sh = None, (bias.contiguous() if bias is not None else None)
-        return pack_conv2d_k1_weight(conv.weight), sc, sh
-    ws, scale, shift = _cache(owner).get(key + "/k1_f16s", srcs, build)
+    ws, scale, shift = _packed_affine(owner, key + "/k1_f16s", conv, bn, pack_conv2d_k1_weight, bias=True)
     return conv2d_k1_f16s_hip(x, ws, conv.out_channels, scale, shift, relu, xb)
 
 
@@ -745,19 +724,6 @@ def conv3d_pointwise_bf16s_hip(x, wsplit, Cout, scale, shift, relu, nterms):
     return out
 
 
-def _convbn_params(owner, key, conv, bn):
-    """(wpack, scale, shift) of a Conv3d(+BN) pair, cached on `owner`."""
-    srcs = [conv.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-
-    def build():
-        wp = pack_conv_weight(conv.weight)
-        if bn is None:
-            return wp, None, None
-        s, b = fold_bn(bn)
-        return wp, s, b
-    return _cache(owner).get(key, srcs, build)
-
-
 def _conv_geometry(conv):
     k, s, p = conv.kernel_size, conv.stride, conv.padding
     assert k[0] == k[1] == k[2] and s[0] == s[1] == s[2] and p[0] == p[1] == p[2] == k[0] // 2
@@ -770,26 +736,16 @@ def run_convbn(owner, key, conv, bn, x, relu, residual=None, gate=None):
     k, s = _conv_geometry(conv)
     if CONV_ENGINE != "f32" and k == 3 and s in (1, 2) and conv.out_channels > 1:
         nterms = _tiled_nterms()
-        srcs = [conv.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-
-        def build():
-            sc, sh = fold_bn(bn) if bn is not None else (None, None)
-            return pack_conv_weight_bf16s(conv.weight, nterms), sc, sh
-        ws, scale, shift = _cache(owner).get(key + ("/f16s" if nterms == 19 else "/bf16s"), srcs, build)
+        ws, scale, shift = _packed_affine(owner, key + ("/f16s" if nterms == 19 else "/bf16s"), conv, bn,
+                                          lambda w: pack_conv_weight_bf16s(w, nterms))
         return conv3d_bf16s_hip(x, ws, conv.out_channels, scale, shift, relu, nterms, residual, gate, stride=s)
     if (CONV_ENGINE != "f32" and k == 3 and s == 1 and conv.out_channels == 1 and conv.in_channels in (16, 32, 64)
             and residual is None and gate is None):
         nterms = _head_nterms()
-        srcs = [conv.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-
-        def build_head():
-            sc, sh = fold_bn(bn) if bn is not None else (None, None)
-            return pack_head_weight_bf16s(conv.weight, nterms), sc, sh
-        ws, scale, shift = _cache(owner).get(key + "/head_%d" % nterms, srcs, build_head)
+        ws, scale, shift = _packed_affine(owner, key + "/head_%d" % nterms, conv, bn, lambda w: pack_head_weight_bf16s(w, nterms))
         return conv3d_head_bf16s_hip(x, ws, scale, shift, relu, nterms)
-    wp, scale, shift = _convbn_params(owner, key, conv, bn)
+    wp, scale, shift = _packed_affine(owner, key, conv, bn, pack_conv_weight)
     return conv3d_hip(x, wp, scale, shift, k, s, relu, residual, gate)
-
 
 
 TRAIN_HIP = os.environ.get("SS_TRAIN_HIP", "1") != "0"      # 0: the stock PyTorch layers whenever autograd / batch statistics are needed
