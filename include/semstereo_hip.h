@@ -41,6 +41,16 @@ int ss_abi_version(void);
  * measurement aids) are read from the environment ONCE per process; call this after changing
  * one of them.  No reference counterpart (the reference has no tuning surface). */
 int ss_reload_tuning(void);
+/* "The chip is shared": how many pairs are in flight on the device at once (PairPipeline's lanes), process-wide, default 1.  Read at
+ * launch time by the FILL heuristics of the 3x3x3 conv launchers only -- which output tile a stride-1 layer gets, which form a
+ * stride-2 layer -- whose thresholds count workgroups: a launch that is one of N in flight need not cover the chip by itself and gets
+ * the larger, cheaper-per-MFMA tile.  Nothing that fixes the summation order reads it (chunk-blocked accumulation stays a property
+ * of the LAYER's own per-pair size), and every tile candidate gives the same bits, so the value -- and a race on it between threads
+ * -- changes speed only, never results.  Clamped to [1, 64].  ss_set_fill_hint returns the PREVIOUS value (to restore it);
+ * ss_get_fill_hint returns the value the launchers use now, i.e. the environment override SS_FILL_HINT (>= 1, read with the other
+ * tuning switches) if that is set.  No reference counterpart. */
+int ss_set_fill_hint(int pairs_in_flight);
+int ss_get_fill_hint(void);
 /* Static, human-readable text for an ss_status. */
 const char* ss_status_string(int status);
 /* hipGetErrorString of the last SS_ERR_LAUNCH on this thread ("" if none). */

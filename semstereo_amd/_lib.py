@@ -120,7 +120,8 @@ _SIGNATURES = {
     "ss_disparity_metrics_fwd": [_P] * 7 + [_I, _I, ctypes.c_longlong] + [ctypes.c_float] * 6 + [_I, _P, _P, _P, _P, ctypes.c_longlong, _P],
     "ss_seg_confusion_fwd": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_longlong, ctypes.c_longlong, _P, _I, _P, ctypes.c_longlong, _P],
 }
-EXPORTS = sorted(list(_SIGNATURES) + ["ss_abi_version", "ss_status_string", "ss_last_hip_error", "ss_ssr_param_count", "ss_reload_tuning"])
+EXPORTS = sorted(list(_SIGNATURES) + ["ss_abi_version", "ss_status_string", "ss_last_hip_error", "ss_ssr_param_count", "ss_reload_tuning",
+                                           "ss_set_fill_hint", "ss_get_fill_hint"])
 
 _lib = None
 
@@ -145,6 +146,10 @@ def load():
     lib.ss_last_hip_error.restype = ctypes.c_char_p
     lib.ss_reload_tuning.restype = _I
     lib.ss_reload_tuning.argtypes = []
+    lib.ss_set_fill_hint.restype = _I          # (returns the previous value, not a status)
+    lib.ss_set_fill_hint.argtypes = [_I]
+    lib.ss_get_fill_hint.restype = _I
+    lib.ss_get_fill_hint.argtypes = []
     if lib.ss_abi_version() != ABI_VERSION:
         raise SemStereoHipError(f"ABI mismatch: library {lib.ss_abi_version()} != binding {ABI_VERSION}; rebuild")
     for name, argtypes in _SIGNATURES.items():

@@ -30,6 +30,7 @@ ss::Tuning read_tuning() {
     if (t.deconv_groups > 2) t.deconv_groups = -1;
     t.deconv_stream = env_int("SS_DECONV_STREAM");
     t.wgrad_coop = env_int("SS_WGRAD_COOP");
+    t.fill_hint = env_int("SS_FILL_HINT");
     return t;
 }
 
@@ -37,6 +38,8 @@ ss::Tuning read_tuning() {
 ss::Tuning g_tuning[2];
 std::atomic<int> g_tuning_slot{-1};
 std::mutex g_mutex;
+std::atomic<int> g_fill_hint{1};            // ss_set_fill_hint(): pairs in flight on the chip
+constexpr int kMaxFillHint = 64;
 std::unordered_map<unsigned long long, int> g_lds_set;      // (kernel address ^ device) -> bytes granted
 }
 
@@ -58,6 +61,12 @@ const Tuning& tuning() {
         }
     }
     return g_tuning[slot];
+}
+
+int fill_hint() {
+    const int env = tuning().fill_hint;
+    const int h = env >= 1 ? env : g_fill_hint.load(std::memory_order_relaxed);
+    return h < 1 ? 1 : (h > kMaxFillHint ? kMaxFillHint : h);
 }
 
 int ensure_dynamic_lds(const void* kernel, int bytes) {
@@ -102,7 +111,13 @@ extern "C" int ss_reload_tuning(void) {
     return SS_OK;
 }
 
-extern "C" int ss_abi_version(void) { return 20; }   // 20: + ss_ssr_upsample_train_fwd / _bwd (the SSR_upsample head trained on HIP); 19: ss_batchnorm_bwd_pg takes the forward's bias (ReLU mask from x when y is NULL); 18: + ss_group_normalise_fwd / _bwd; 17: + ss_concat_sampled_bwd (the sparse concat volume's backward in one pass); 16: + ss_batchnorm_train_fwd_rs, ss_batchnorm_bwd_pg (running statistics and float parameter gradients inside the kernels); 15: + ss_sample_strength_bwd_ws; 14: + ss_regression_topk_patched_fwd (the classifier's patch sum folded into the top-2 soft-argmax); 13: + ss_conv3d_wgrad_bf16s_fwd (weight gradients on the bf16 matrix core); 12: + ss_conv3d_gather_fwd (sparse concat formed inside concat_stem), ss_ssr_upsample2_fwd; 11: + training leftovers (ss_batchnorm_train_res_fwd/_bwd: residual + ReLU inside the BatchNorm apply; ss_window_attention_core_pad_bwd; the attention-tail backward kernels); 10: + training side (ss_batchnorm_train_fwd/_bwd, ss_channel_sum_fwd, ss_depthwise_patch_wgrad_fwd, ss_channel_gate_bwd_logits, ss_window_attention_core_bwd), ss_tool_copy_fwd; 9: + ss_concat_sampled_presplit_fwd, ss_conv3d_presplit_fwd (pre-split operands, LDS-DMA staging); 8: channels-last hand-off inside the classifiers (ss_conv3d_bf16s_cl_fwd, ss_conv3d_head_bf16s_cl_fwd); 7: disparity ranges (dmin, ndisp) instead of maxdisp, ss_conv3d_wgrad_fwd, backward entry points; 6: + ss_channel_att_logits_fwd, ss_upsample_softmax_regression_fwd (5: ss_reload_tuning)
+extern "C" int ss_set_fill_hint(int pairs_in_flight) {
+    return g_fill_hint.exchange(pairs_in_flight < 1 ? 1 : (pairs_in_flight > kMaxFillHint ? kMaxFillHint : pairs_in_flight), std::memory_order_relaxed);
+}
+
+extern "C" int ss_get_fill_hint(void) { return ss::fill_hint(); }
+
+extern "C" int ss_abi_version(void) { return 20; }   // (still 20: + ss_set_fill_hint / ss_get_fill_hint, symbols added and nothing changed) 20: + ss_ssr_upsample_train_fwd / _bwd (the SSR_upsample head trained on HIP); 19: ss_batchnorm_bwd_pg takes the forward's bias (ReLU mask from x when y is NULL); 18: + ss_group_normalise_fwd / _bwd; 17: + ss_concat_sampled_bwd (the sparse concat volume's backward in one pass); 16: + ss_batchnorm_train_fwd_rs, ss_batchnorm_bwd_pg (running statistics and float parameter gradients inside the kernels); 15: + ss_sample_strength_bwd_ws; 14: + ss_regression_topk_patched_fwd (the classifier's patch sum folded into the top-2 soft-argmax); 13: + ss_conv3d_wgrad_bf16s_fwd (weight gradients on the bf16 matrix core); 12: + ss_conv3d_gather_fwd (sparse concat formed inside concat_stem), ss_ssr_upsample2_fwd; 11: + training leftovers (ss_batchnorm_train_res_fwd/_bwd: residual + ReLU inside the BatchNorm apply; ss_window_attention_core_pad_bwd; the attention-tail backward kernels); 10: + training side (ss_batchnorm_train_fwd/_bwd, ss_channel_sum_fwd, ss_depthwise_patch_wgrad_fwd, ss_channel_gate_bwd_logits, ss_window_attention_core_bwd), ss_tool_copy_fwd; 9: + ss_concat_sampled_presplit_fwd, ss_conv3d_presplit_fwd (pre-split operands, LDS-DMA staging); 8: channels-last hand-off inside the classifiers (ss_conv3d_bf16s_cl_fwd, ss_conv3d_head_bf16s_cl_fwd); 7: disparity ranges (dmin, ndisp) instead of maxdisp, ss_conv3d_wgrad_fwd, backward entry points; 6: + ss_channel_att_logits_fwd, ss_upsample_softmax_regression_fwd (5: ss_reload_tuning)
 
 extern "C" const char* ss_status_string(int status) {
     switch (status) {

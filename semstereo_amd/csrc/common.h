@@ -37,8 +37,12 @@ struct Tuning {
     int deconv_groups;    // SS_DECONV_GROUPS (fp16 transposed convs): 0 = all 8 parity classes per workgroup, 1 = two class groups, 2 = + chunk-blocked accumulation; unset: by layer size
     int deconv_stream;    // SS_DECONV_STREAM 0/1: plain / nontemporal stores of the fp16 transposed convs' output; unset: by output size
     int wgrad_coop;       // SS_WGRAD_COOP=0: the per-wave form of the stride-1 bf16 weight gradient instead of the cooperative one (r06)
+    int fill_hint;        // SS_FILL_HINT >= 1: overrides ss_set_fill_hint() (1 = every launch sized as if alone on the chip)
 };
 const Tuning& tuning();
+// Pairs in flight on the chip (ss_set_fill_hint, default 1; SS_FILL_HINT overrides): read at launch time by the FILL heuristics of the
+// conv launchers only -- which tile, which stride-2 form -- never by anything that decides the summation order.
+int fill_hint();
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device) instead of once per launch.
 int ensure_dynamic_lds(const void* kernel, int bytes);

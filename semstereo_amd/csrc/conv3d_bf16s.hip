@@ -91,9 +91,24 @@ struct BCfg {
 #ifndef SS_WLDS_NT4
 #define SS_WLDS_NT4 0             // 1: the 4-row tile also takes its weight fragments through LDS (variant builds)
 #endif
-constexpr bool wlds_form(int S, int NT, int NTERMS, int MT, int KD, bool gather = false) {
+#ifndef SS_ACCB_PASSES
+#define SS_ACCB_PASSES 2          // passes over a chunk's K-steps of the chunk-blocked 4-row tile (acc_passes below); 1: the single-pass form, which spills (variant builds, for A/B)
+#endif
+#ifndef SS_ACCB_PASSES_44
+#define SS_ACCB_PASSES_44 2       // ... of its 4 x 4 x 32 form alone (1: one pass with the rest of the two-pass form's register diet: 235 VGPRs, no scratch; variant builds)
+#endif
+// (accb: the chunk-blocked 4-row tile walks its rows in two passes per chunk and reads the fragments of every pass from the LDS copy)
+constexpr bool wlds_form(int S, int NT, int NTERMS, int MT, int KD, bool gather = false, bool accb = false) {
     // (the gather form's tile has no LDS left for the 28 KB slab at two workgroups per CU)
-    return NTERMS == 19 && S == 1 && (NT == 1 || (SS_WLDS_NT4 && NT == 4 && !gather)) && MT == 1 && KD == 3;       // (NT = 2: 43 B/clk, measured +3 %: left alone)
+    return NTERMS == 19 && S == 1 && (NT == 1 || ((SS_WLDS_NT4 || (accb && SS_ACCB_PASSES > 1)) && NT == 4 && !gather)) && MT == 1 && KD == 3;       // (NT = 2: 43 B/clk, measured +3 %: left alone)
+}
+// Chunk-blocked accumulation on the 4-row tile: a second accumulator set for all four rows does not fit beside the first (64 + 64 of
+// 256 registers: 15 / 46 spilled on the 4 x 4 / 2 x 8 tile).  The chunk's K-steps are therefore walked TWICE, each pass over two of
+// the wave's rows with a 32-register second set that is folded into `acc` at the end of the pass.  A row's products are still summed
+// from zero in K order and added to `acc` once per chunk: the same bits.  What a second pass re-reads are the weight fragments, which
+// this form keeps in LDS (wlds_form).
+constexpr int acc_passes(int S, int NT, int NTERMS, int MT, int KD, bool accb, bool gather) {
+    return (accb && NT == 4 && SS_ACCB_PASSES > 1 && wlds_form(S, NT, NTERMS, MT, KD, gather, accb)) ? 2 : 1;
 }
 // gather form: per halo position one candidate word and two attention words (this tile's, the next tile's), each thread's
 // own positions p = tid + 256 i -> 3 x NPOS x 256 floats
@@ -109,8 +124,9 @@ constexpr int HEAD_PATCH = 6 * 6 * 34;        // a 4 x 4 x 32 tile's contributio
 // (test_hot_segment_batch_invariance_at_the_sharded_batch_sizes).  fp16 form only.  It is on for every stride-2 layer, every
 // 2-D layer, and the stride-1 3-D layers that at batch 1 are too small for the 4-row tile -- the deep, narrow layers with the
 // longest K (conv2 / conv4 of the hourglasses: K = 1728 / 3456): there the second accumulator set fits the registers of the 1- and
-// 2-row tiles they run on at small batch; when a larger batch moves them onto the 4-row tile that variant spills 16 registers
-// (+7 %, measured on the stem shape).  The big 4-row layers (concat_stem, classif.0, hourglass2.conv2) keep the single chain.
+// 2-row tiles they run on at small batch; when a larger batch -- or the fill hint of a pipelined call -- moves them onto the 4-row
+// tile, that variant walks the chunk in two passes of two rows (acc_passes above; one pass with a second set for all four rows
+// spilled 15 - 46 registers).  The big 4-row layers (concat_stem, classif.0, hourglass2.conv2) keep the single chain.
 #ifndef SS_ACC_BLOCKED
 #define SS_ACC_BLOCKED 1                  // 0: single chains everywhere (tools/build_variant.sh, for A/B measurements)
 #endif
@@ -171,7 +187,10 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
     // step's 2 KB of weight fragments every 96-192 cycles ask the vector L1 for 43-85 B/clk of its 64.  The chunk's fragments
     // (14 steps x 2 terms, 28 KB) are then brought into LDS once per workgroup by LDS-DMA loads (no registers) and read
     // from there by the four waves (deconv3d_bf16s.hip has the measurement: -11 %).
-    constexpr bool WLDS = wlds_form(S, NT, NTERMS, MT, KD, GATHER);
+    constexpr bool WLDS = wlds_form(S, NT, NTERMS, MT, KD, GATHER, ACCB);
+    // LOCAL: the register diet that goes with it (fragment addresses per K-step, halo index arithmetic per tile; see read_b, make_poff)
+    constexpr bool LOCAL = acc_passes(S, NT, NTERMS, MT, KD, ACCB, GATHER) > 1;
+    constexpr int PASSES = !LOCAL ? 1 : (TD == 4 ? SS_ACCB_PASSES_44 : 2), NR = NT / PASSES;       // rows of a pass over the chunk's K-steps
     static_assert(!ACCB || NTERMS == F16X3, "chunk-blocked accumulation: fp16 form only");
     static_assert(!WLDS || MS == 1, "the LDS copy of the weights is one channel tile's");
     using C = BCfg<S, NT, TD, TH, KD, NC, WLDS ? ((KD * 9 + 1) / 2) * 2 * 64 : 0, MS, gather_slots(GATHER, S, TD, TH, KD) + (HEAD ? HEAD_WSLOTS : 0)>;
@@ -261,9 +280,11 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
         int ow0, oh0, od0;
         tile_origin(tile, ow0, oh0, od0);
         const int iw0 = ow0 * S - 1, ih0 = oh0 * S - 1, id0 = od0 * S - KD / 2;
+        int ptid = tid;                // (LOCAL: opaque, so that the positions' index arithmetic is redone per tile instead of living in registers -- or scratch -- through the K loop)
+        if constexpr (LOCAL) asm volatile("" : "+v"(ptid));
 #pragma unroll
         for (int i = 0; i < C::NPOS; ++i) {
-            const int p = tid + 256 * i;
+            const int p = ptid + 256 * i;
             const int sx = p % C::IW;
             const int wx = (DEINT && !DEINT_W) ? (sx < (C::IW + 1) / 2 ? 2 * sx : 2 * (sx - (C::IW + 1) / 2) + 1) : sx;      // (DEINT: slot -> column)
             int r = p / C::IW;
@@ -497,31 +518,41 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
         // times: measured 3.3e-7 ... 6.2e-7 of the output's rms for K = 864 ... 3456 against float64 (tools/err_stages.py),
         // 1.2 - 3.5x the fp32 CPU convolution of the reference, which sums in blocks too; chunk-blocked it is 1.9e-7 ... 2.3e-7
         // whatever K, at or below the CPU's.  Where the second set fits the register budget it costs no time (stride-2
-        // forms 85.0 vs 85.5 us, the 1 x 4 tile 68.8 vs 68.2); the 4-row tiles would spill (+7 %) and keep the single chain.
-        f32x16 tacc[ACCB ? MT * NT : 1];
-        if constexpr (ACCB) {
-#pragma unroll
-            for (int i = 0; i < MT * NT; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) tacc[i][r] = 0.f;
-        }
+        // forms 85.0 vs 85.5 us, the 1 x 4 tile 68.8 vs 68.2); the big 4-row layers would spill (+7 %) and keep the single chain.
+        // (the 4-row tile: in PASSES passes of NR rows each, see acc_passes)
+        static_assert(PASSES == 1 || (WLDS && MT == 1), "a second pass re-reads the weight fragments from LDS");
+        f32x16 tacc[ACCB ? MT * NR : 1];
 
         // B fragments are read one row GROUP ahead of their MFMAs.  With RP = 2 the MFMAs of two rows
         // alternate so that no two consecutive ones share an accumulator (SS_ROW_PAIR; no gain measured).
         constexpr int RP = (NT >= 2) ? ((S == 2) ? SS_ROW_PAIR_S2 : SS_ROW_PAIR) : 1;
-        static_assert(NT % RP == 0, "rows are processed in whole groups");
+        static_assert(NR % RP == 0, "rows are processed in whole groups");
         uint4 bcur[RP][NC], bnxt[RP][NC];
+        int hv = half;
         auto read_b = [&](uint4 (&dst)[NC], int s, int i) {
             const int ta = 2 * s, tb = 2 * s + 1;
             constexpr int kwo[3] = {0, DEINT ? (C::IW + 1) / 2 : 1, DEINT ? 1 : 2};            // slot offset of tap column kw
             const int offa = ((ta / 9) * C::IH + (ta / 3) % 3) * C::IW + kwo[ta % 3];
             const int offb = (tb < C::KT) ? ((tb / 9) * C::IH + (tb / 3) % 3) * C::IW + kwo[tb % 3] : 0;
-            const int slot = lane_pos + i * S * C::IW + (half ? offb : offa);
+            // (LOCAL: the two-pass form derives the lane half's slot from `hv`, opaque once per K-step: as invariants of the chunk loop the 14
+            // steps' fragment addresses were hoisted out of it, one register each, and then spilled)
+            const int hf = LOCAL ? hv : half;
+            const int slot = lane_pos + i * S * C::IW + (LOCAL ? offa + hf * (offb - offa) : (hf ? offb : offa));
 #pragma unroll
-            for (int c = 0; c < NC; ++c) dst[c] = lds[(tb >= C::KT && half) ? ZSLOT : c * C::CS + slot];
+            for (int c = 0; c < NC; ++c) dst[c] = lds[(tb >= C::KT && hf) ? ZSLOT : c * C::CS + slot];
         };
 #pragma unroll
-        for (int r = 0; r < RP; ++r) read_b(bcur[r], 0, r);
+        for (int ps = 0; ps < PASSES; ++ps) {
+        const int rb = ps * NR;                                // first row of this pass
+        if constexpr (LOCAL) asm volatile("" : "+v"(hv));
+        if constexpr (ACCB) {
+#pragma unroll
+            for (int i = 0; i < MT * NR; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tacc[i][r] = 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < RP; ++r) read_b(bcur[r], 0, rb + r);
         if (WLDS) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) aq[0][0][c] = lds[WL + c * 64 + lane];
@@ -533,6 +564,7 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
             // wait-count pass cannot tell how many loads are younger than the one it waits for and falls back to
             // vmcnt(0/1) -- every K-step then waited for the input loads it had just issued (seen in the ISA).  Past the
             // end, the last fragment is requested again and the input loads get an offset beyond the buffer (no access).
+            if constexpr (LOCAL) asm volatile("" : "+v"(hv));
             if (!WLDS) {
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
@@ -546,6 +578,7 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
                 for (int c = 0; c < NC; ++c) aq[(s + 1) % AR][0][c] = lds[WL + ((s + 1) * 2 + c) * 64 + lane];
             }
 #ifndef SS_EXP_CONV_KEEP          // (timing experiment, wrong results: no input loads after a workgroup's first chunk -- the staged data keeps its statistics)
+            if (ps == 0)
 #pragma unroll
             for (int q = s * QS; q < (s + 1) * QS && q < NQ; ++q)
                 rin[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
@@ -557,11 +590,11 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
 #pragma unroll
                 for (int c = 0; c < NC; ++c) a[mt][c] = aq[s % AR][mt][c];
 #pragma unroll
-            for (int i0 = 0; i0 < NT; i0 += RP) {
+            for (int i0 = 0; i0 < NR; i0 += RP) {
 #pragma unroll
                 for (int r = 0; r < RP; ++r) {
-                    if (i0 + RP < NT) read_b(bnxt[r], s, i0 + RP + r);
-                    else if (s + 1 < KSTEPS) read_b(bnxt[r], s + 1, r);
+                    if (i0 + RP < NR) read_b(bnxt[r], s, rb + i0 + RP + r);
+                    else if (s + 1 < KSTEPS) read_b(bnxt[r], s + 1, rb + r);
                 }
                 // cross terms (a term, b term), smallest first; rows of the group alternate
                 constexpr int NP = (NTERMS == 6) ? 6 : 3;
@@ -572,7 +605,7 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
                     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                         for (int r = 0; r < RP; ++r) {
-                            f32x16& dst = ACCB ? tacc[ACCB ? mt * NT + i0 + r : 0] : acc[mt * NT + i0 + r];
+                            f32x16& dst = ACCB ? tacc[ACCB ? mt * NR + i0 + r : 0] : acc[mt * NT + rb + i0 + r];
                             if (F16)
                                 dst = __builtin_amdgcn_mfma_f32_32x32x16_f16(
                                     __builtin_bit_cast(f16x8, a[mt][pa[p]]), __builtin_bit_cast(f16x8, bcur[r][pb[p]]), dst, 0, 0, 0);
@@ -592,6 +625,16 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
             }
             __builtin_amdgcn_sched_barrier(0);     // keep each step's loads inside the step
         }
+        if constexpr (ACCB && PASSES > 1) {
+#pragma unroll
+            for (int i = 0; i < NR; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[rb + i][r] += tacc[i][r];
+            // (the fold is pinned here: sunk towards the next use of `acc`, it kept this pass's second set alive through the next pass)
+#pragma unroll
+            for (int i = 0; i < NR; ++i) asm volatile("" : "+v"(acc[rb + i]));
+        }
+        }       // passes
         // steps 14 .. 14+AP-1 of this chunk are steps 0 .. AP-1 of the next: re-base the fragment ring
         if (!WLDS) {
             uint4 tq[AP][MT][NC];
@@ -608,7 +651,7 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
 #pragma unroll
                     for (int c = 0; c < NC; ++c) aq[k][mt][c] = tq[k][mt][c];
         }
-        if constexpr (ACCB) {
+        if constexpr (ACCB && PASSES == 1) {
 #pragma unroll
             for (int i = 0; i < MT * NT; ++i)
 #pragma unroll
@@ -889,7 +932,7 @@ template <int S, int NT, int TD, int TH, int NTERMS, bool GATED, int MT, int KD 
 int launch_bgm(const float* in, const void* wsplit, const float* scale, const float* shift, const float* residual,
               const float* gate, float* out, int B, int Cin, int D, int H, int W, int Cout, int relu, hipStream_t st,
               const float* cand = nullptr, const float* catt = nullptr, const float* in2 = nullptr, int bsplit = 0, int csplit = 0) {
-    using C = BCfg<S, NT, TD, TH, KD, (NTERMS == 6) ? 3 : 2, wlds_form(S, NT, NTERMS, MT, KD, GATHER) ? ((KD * 9 + 1) / 2) * 2 * 64 : 0, MS,
+    using C = BCfg<S, NT, TD, TH, KD, (NTERMS == 6) ? 3 : 2, wlds_form(S, NT, NTERMS, MT, KD, GATHER, ACCB) ? ((KD * 9 + 1) / 2) * 2 * 64 : 0, MS,
                    gather_slots(GATHER, S, TD, TH, KD) + (HEAD ? HEAD_WSLOTS : 0)>;
     const int Do = (D + 2 * (KD / 2) - KD) / S + 1, Ho = (H - 1) / S + 1, Wo = (W - 1) / S + 1;
     const int tiles_w = ss::ceil_div(Wo, 32), tiles_h = ss::ceil_div(Ho, TH), tiles_d = ss::ceil_div(Do, TD);
@@ -921,7 +964,8 @@ int launch_bg(const float* in, const void* wsplit, const float* scale, const flo
     // stride 2: two output tiles per wave (the activation staging is then shared: 154 vs 191 us on the largest layer)
     // unless that leaves fewer workgroups than CUs (57 vs 41 us on the smallest)
     const int Do = (D - 1) / S + 1, Ho = (H - 1) / S + 1, Wo = (W - 1) / S + 1;
-    const long long wg2 = (long long)ss::ceil_div(Wo, 32) * ss::ceil_div(Ho, TH) * ss::ceil_div(Do, TD) * ss::ceil_div(Cout, 64) * B;
+    // (ss::fill_hint(): pairs in flight on the chip beside this launch's own -- the fill thresholds below count their workgroups too)
+    const long long wg2 = (long long)ss::ceil_div(Wo, 32) * ss::ceil_div(Ho, TH) * ss::ceil_div(Do, TD) * ss::ceil_div(Cout, 64) * B * ss::fill_hint();
     // ... and, since r03, the 64 channels split over the waves (MS = 2: wave = (row pair, 32 channels)) instead of two channel
     // tiles per wave: the same MFMAs and staging with half the weight-fragment fetches (SS_CONV_S2_MT1=0: the r02 form)
     if constexpr (S == 2 && NT == 1 && TD * TH == 4 && !GATED) {      // (no layer gates a stride-2 conv; its MS form would spill)
@@ -996,7 +1040,11 @@ static int conv3d_bf16s_impl(const float* in, const void* wsplit, const float* s
         return (long long)ss::ceil_div(Wo, 32) * ss::ceil_div(Ho, th) * ss::ceil_div(Do, td) * ss::ceil_div(Cout, 32) * B;
     };
     const int forced = ss::tuning().conv_tile;
-    int tile = (blocks(2, 8) >= 512) ? 0 : ((blocks(1, 8) >= 512) ? 1 : 2);
+    // The tile is chosen for FILL: the largest whose workgroups still cover the chip.  A launch that shares the chip with other pairs'
+    // launches (PairPipeline's lanes) is not alone in filling it: ss::fill_hint() scales the count by the pairs in flight.  Every tile
+    // gives the same bits (the summation order is the layer's, see ACCB), so the hint -- and a race on it -- changes speed only.
+    const long long hint = ss::fill_hint();
+    int tile = (blocks(2, 8) * hint >= 512) ? 0 : ((blocks(1, 8) * hint >= 512) ? 1 : 2);
     if (forced >= 0 && forced <= 2) tile = forced;
     // chunk-blocked accumulation: decided by the LAYER (what ONE pair of it offers the chip), not by this launch's batch or tile
     const bool small_layer = blocks(2, 8) / B < 512;

@@ -39,7 +39,8 @@ extern "C" int ss_conv3d_gather_fwd(const float* right, const float* cand, const
         return (long long)ss::ceil_div(W, 32) * ss::ceil_div(H, th) * ss::ceil_div(nd, td) * ss::ceil_div(Cout, 32) * B;
     };
     const int forced = ss::tuning().conv_tile;
-    int tile = (blocks(2, 8) >= 512) ? 0 : ((blocks(1, 8) >= 512) ? 1 : 2);
+    const long long hint = ss::fill_hint();                    // (pairs in flight: speed only, as in conv3d_bf16s_impl)
+    int tile = (blocks(2, 8) * hint >= 512) ? 0 : ((blocks(1, 8) * hint >= 512) ? 1 : 2);
     if (forced >= 0 && forced <= 2) tile = forced;
     const bool accb = SS_ACC_BLOCKED && blocks(2, 8) / B < 512;
     const int r = (relu ? 1 : 0) | (partial ? 2 : 0);

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib
 from . import deferred as dfr
 from . import modules as M
 from . import ops, ops_unsigned
@@ -43,6 +44,23 @@ def overlap_override(value):
         yield
     finally:
         _TLS.overlap = prev
+
+
+@contextlib.contextmanager
+def fill_hint(pairs_in_flight):
+    """Tell the library's fill heuristics, for the launches issued inside the block, that `pairs_in_flight` pairs share the chip
+    (ss_set_fill_hint: the conv launchers then pick their tile for a chip the other pairs help to fill); the previous value is put
+    back on the way out, also when the block raises.  None: leave the hint alone.  Process-wide and speed only: every tile candidate
+    gives the same bits, so two threads racing on the value cannot change a result (include/semstereo_hip.h)."""
+    if pairs_in_flight is None:
+        yield
+        return
+    lib = _lib.load()
+    prev = lib.ss_set_fill_hint(int(pairs_in_flight))
+    try:
+        yield
+    finally:
+        lib.ss_set_fill_hint(prev)
 
 
 def _side_stream(device):
@@ -446,7 +464,7 @@ class PairPipeline:
             for _ in range(self.LANE_WARM_CALLS if self.warmed_lanes == self.nlanes else 0):
                 for lane in self.lanes:
                     lane.wait_stream(cur)
-                    with torch.cuda.stream(lane), torch.no_grad(), overlap_override(False):
+                    with torch.cuda.stream(lane), torch.no_grad(), overlap_override(False), fill_hint(self.nlanes):
                         self.segment(*inputs)
                     for t in inputs:
                         if isinstance(t, torch.Tensor):
@@ -481,8 +499,10 @@ class PairPipeline:
             M.E.drop_retired()              # entries replaced by calls OUTSIDE the pipeline (a plain call between two pipelined ones): nothing in flight reads them
         gen = M.E.cache_generation()
         # the lanes ARE the concurrency: the within-pair second stream on top of them costs 0.8 % (4 lanes: 525.7 vs 521.4 pairs/s);
-        # passed down per thread (overlap_override), the shared module is not written to
-        with torch.cuda.stream(lane), torch.no_grad(), overlap_override(False if self.nlanes > 1 else None):
+        # passed down per thread (overlap_override), the shared module is not written to.  For the same reason a launch need not fill
+        # the chip by itself: the conv launchers are told how many pairs are in flight (fill_hint) for the duration of the call
+        with torch.cuda.stream(lane), torch.no_grad(), overlap_override(False if self.nlanes > 1 else None), \
+                fill_hint(self.nlanes if self.nlanes > 1 else None):
             out = self.segment(*inputs)
         if M.E.cache_generation() != gen and self.nlanes > 1:
             # A cache entry was (re)built during this call -- load_state_dict / an in-place weight update, an engine switch, a shape
