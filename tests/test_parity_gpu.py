@@ -1278,17 +1278,9 @@ def test_deconv3d_split_bf16_engine(sa, case, nterms):
     assert e_split <= (1.5 * e_f32 + 1e-6 if nterms != 3 else 4e-5), (e_split, e_f32)
 
 
-F16_RANGE_CASES = {
-    # name: (multiplier per input channel (32 of them), weight multiplier per output channel (32))
-    "tensor_1e-6": (lambda c: 1e-6, lambda c: 1.0),
-    "tensor_1e+6": (lambda c: 1e6, lambda c: 1.0),
-    "tensor_1e-20_weights_1e+12": (lambda c: 1e-20, lambda c: 1e12),
-    "channels_1e-6_to_1e+6": (lambda c: 10.0 ** (-6 + 12 * c / 31), lambda c: 1.0),
-    "channels_1e+6_to_1e-6": (lambda c: 10.0 ** (6 - 12 * c / 31), lambda c: 1.0),
-    "out_channels_1e-8_to_1e+8": (lambda c: 1.0, lambda c: 10.0 ** (-8 + 16 * c / 31)),
-    "one_huge_channel": (lambda c: 3e4 if c == 17 else 1e-3, lambda c: 1.0),
-    "tensor_1e-30": (lambda c: 1e-30, lambda c: 1.0),
-}
+# the range cases of every kernel on the two-term fp16 form: one table, tests/f16_model.py (called with a channel index alone it is
+# the 32-channel table this test has always used)
+from f16_model import F16_RANGE_CASES  # noqa: E402
 
 
 @pytest.mark.parametrize("stride", [1, 2])
