@@ -151,6 +151,15 @@ int ss_stem_left_fwd(const float* q, const float* att, float* out, int B, int Co
  * row pair*64 + tap*2 + c is (scale *) W[2*pair + c, :C, tap] (rows 54-63 of every pair zero). */
 int ss_stem_left_fused_fwd(const float* left, const void* wsplit, const float* att, float* out, int B, int C,
                            int Cout, int nd, int H, int W, int nterms, ss_stream_t stream);
+/* The same on the two-term fp16 form (f16x3 engine), Q by shifts: per (kh, kw) the matrix product's B operand is the left
+ * map's tile SHIFTED by that offset, so every lane receives the Q values of its own output and the 27 multiply-adds read
+ * them from the accumulator registers (no Q tile in LDS).  C = Cout = 32, nd in {6, 24, 32}; anything else is
+ * SS_ERR_UNSUPPORTED.  wsplit = ss_pack_stem_left_weights_f16s of the left-half weights w [Cout, C, 27] (tap = kd*9+kh*3+kw):
+ * 73728 fp16 terms in fragment order (two terms of w / u, u a power of two per (tap, output channel)) followed by the 864
+ * floats u; 150912 bytes, 16-byte aligned. */
+int ss_stem_left_mfma_fwd(const float* left, const void* wsplit, const float* att, float* out, int B, int C,
+                          int Cout, int nd, int H, int W, ss_stream_t stream);
+int ss_pack_stem_left_weights_f16s(const float* w, void* wsplit, int Cout, int C, ss_stream_t stream);
 /* Fused form of models/SemStereo.py:291-292: mean over channels of left * warp(right):
  * x,y [B,C,H,W], disp [B,nd,H,W] -> [B,nd,H,W] */
 int ss_warp_correlation_fwd(const float* x, const float* y, const float* disp, float* out,

@@ -32,6 +32,8 @@ _SIGNATURES = {
     "ss_conv3d_presplit_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "ss_stem_left_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "ss_stem_left_fused_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "ss_stem_left_mfma_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ss_pack_stem_left_weights_f16s": [_P, _P, _I, _I, _P],
     "ss_warp_correlation_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "ss_disparity_regression_fwd": [_P, _P, _I, _I, _I, _I, _I, _P],
     "ss_disparity_regression_bwd": [_P, _P, _I, _I, _I, _I, _I, _P],

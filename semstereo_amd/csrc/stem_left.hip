@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "split_bf16.h"
+#include "split_f16.h"
 
 namespace {
 
@@ -304,4 +305,246 @@ extern "C" int ss_stem_left_fused_fwd(const float* left, const void* wsplit, con
     if (nd == 32) return launch_fused<32>(left, wsplit, att, out, B, Cout, H, W, nterms, st);
     if (nd == 6) return launch_fused<6>(left, wsplit, att, out, B, Cout, H, W, nterms, st);
     return SS_ERR_UNSUPPORTED;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same result with Q never leaving the REGISTERS (f16x3 engine, C = Cout = 32): Q by shifts.  The fused kernel above
+// projects the whole 6 x 34 halo tile (204 -> 224 columns, 54 -> 64 rows per channel pair, six bf16 products: 21 matrix
+// instructions per output position), parks Q in LDS and reads it back shifted.  Here the SHIFT is applied to the matrix
+// product's B operand instead: wave w owns row w of the 4 x 32 tile, and for one (kh, kw) its B fragments are the left map
+// at (row + kh - 1, column + kw - 1) of its 32 positions, read from a halo tile that is staged once per workgroup on two
+// fp16 terms under ONE block exponent (split_f16.h) in channel-innermost 16-byte slots.  The A operand is 32 rows of the
+// left-half weights of that (kh, kw): rows kd * 8 + c, kd = 0..2, c = 8 output channels (rows 24..31 zero), pre-split and
+// pre-scaled per row by the packer below.  2 K-steps x 3 products (w_lo x_hi, w_hi x_lo, w_hi x_hi, in that order) leave
+// in the lane of position p exactly the Q values its own output needs -- Q[kd, c, p + off(kh, kw)], 4 channels per lane half
+// -- so the 27 multiply-adds per output consume them from the accumulator registers: no Q tile in LDS, no barrier in the
+// main loop, no halo of Q, 6.75 matrix instructions per position.  The multiply-adds run in the order of the kernels above
+// ((kh, kw) outer, kd inner), in fp32, on the fp32 att tile.
+//
+// Exceptional values: the 3-D kernels' rule (abs_max<DROP_INF = false>).  An infinity in `left` enters the tile maximum, the
+// block exponent is 255 and the whole workgroup tile is affected (its finite values are scaled below fp16's range), not only
+// the infinity's receptive field.  A NaN in `left` is dropped from the maximum (fmaxf), stays a NaN in both terms and makes
+// Q a NaN at its position for all output channels: every output whose 3 x 3 window holds that position is a NaN, for every
+// candidate (NaN * 0 in the multiply-adds), as in the two kernels above.  Positions outside the image contribute zero.
+// The tile, the block exponent and the order of every sum depend on the layer and the position only, never on the batch.
+namespace {
+
+constexpr int MROWS = 8;                            // output channels per M-tile (3 kd x 8 channels = 24 live rows of 32)
+constexpr int NCG = 32 / MROWS;                     // M-tiles per (kh, kw): Cout = 32
+constexpr int WFRAG_HALVES = NCG * 9 * 2 * 2 * 64 * 8;     // fp16 terms of the packed weights: (channel group, shift, K-step, term, lane, 8); then the inverse scales as floats: (channel group, shift, lane half, kd, 4 channels)
+
+template <int ND>
+__global__ __launch_bounds__(256, 2) void stem_left_mfma(const float* __restrict__ left, const uint4* __restrict__ wfrag,
+                                                          const float4* __restrict__ winv, const float* __restrict__ att,
+                                                          float* __restrict__ out, int H, int W) {
+    constexpr int C = 32, Cout = 32;
+    __shared__ __attribute__((aligned(16))) float atile_s[ND + 2][HH][HW];      // planes -1 and ND are zero (the padding along the candidates)
+    __shared__ uint4 ltile[8][NPOSH];                                           // [channel octet * 2 + term][halo position]: 8 fp16 channels
+    __shared__ float4 uinv[NCG * 9 * 2 * 3];                                    // the weight rows' inverse scales: (channel group, shift, lane half, kd)[4 channels]
+    __shared__ unsigned wmax[4];
+    float (*atile)[HH][HW] = atile_s + 1;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, half = lane >> 5;
+    const int w0 = blockIdx.x * FTW, h0 = blockIdx.y * FTH, b = blockIdx.z;
+    const size_t plane = (size_t)H * W;
+
+    // the att halo tile, as in stem_left_fused
+    {
+        const __amdgpu_buffer_rsrc_t ares = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(att + (size_t)b * ND * plane), 0, (int)min((long long)ND * (long long)plane * 4, 0x7fffffffLL), 0x00020000);
+        constexpr int NE = (ND * NPOSH + 255) / 256;
+        float av[NE];
+#pragma unroll
+        for (int k = 0; k < NE; ++k) {
+            const int e = tid + 256 * k;
+            const int x = e % HW;
+            int r = e / HW;
+            const int y = r % HH, j = r / HH;
+            const int gh = h0 + y - 1, gw = w0 + x - 1;
+            const bool ok = e < ND * NPOSH && (unsigned)gh < (unsigned)H && (unsigned)gw < (unsigned)W;
+            av[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                                                  ares, (int)(ok ? (unsigned)(((size_t)j * plane + (size_t)gh * W + gw) * 4) : 0x80000000u), 0, 0));
+        }
+#pragma unroll
+        for (int k = 0; k < NE; ++k) {
+            const int e = tid + 256 * k;
+            if (e < ND * NPOSH) (&atile[0][0][0])[e] = av[k];
+        }
+        if (tid < NPOSH) {
+            (&atile[-1][0][0])[tid] = 0.f;
+            (&atile[ND][0][0])[tid] = 0.f;
+        }
+    }
+
+    if (tid < NCG * 9 * 2 * 3) uinv[tid] = winv[tid];
+
+    // the left halo tile: 204 positions x 4 channel octets, a thread stages slots tid + 256 k; one block exponent for the tile
+    int e_tile;
+    {
+        const __amdgpu_buffer_rsrc_t lres = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(left + (size_t)b * C * plane), 0, (int)min((long long)C * (long long)plane * 4, 0x7fffffffLL), 0x00020000);
+        const int chan_b = (int)(plane * 4);
+        constexpr int NS = (4 * NPOSH + 255) / 256;
+        float x[NS][8];
+        float m = 0.f;
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const int e = tid + 256 * k;
+            const int p = e % NPOSH, oct = e / NPOSH;
+            const int gh = h0 + p / HW - 1, gw = w0 + p % HW - 1;
+            const bool ok = e < 4 * NPOSH && (unsigned)gh < (unsigned)H && (unsigned)gw < (unsigned)W;
+            const unsigned off = ok ? (unsigned)((8LL * oct * plane + (size_t)gh * W + gw) * 4) : 0x80000000u;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                x[k][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(lres, (int)off, j * chan_b, 0));
+            m = abs_max<false>(x[k], m);
+        }
+        const unsigned wm = wave_max_bits(__float_as_uint(m));
+        if (lane == 0) wmax[wave] = wm;
+        __syncthreads();
+        e_tile = workgroup_exponent(wmax);
+        const float sc = scale_for(e_tile);
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const int e = tid + 256 * k;
+            if (e >= 4 * NPOSH) continue;
+            const int p = e % NPOSH, oct = e / NPOSH;
+            unsigned hi[4], lo[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) split2_pk_f16(x[k][2 * j] * sc, x[k][2 * j + 1] * sc, hi[j], lo[j]);
+            ltile[oct * 2 + 0][p] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+            ltile[oct * 2 + 1][p] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+        }
+    }
+    __syncthreads();
+
+    const float unl = unscale_for(e_tile);
+    const int h = h0 + wave, w = w0 + l31;
+    const bool inside = h < H && w < W;
+    // The 4 weight fragments of a (channel group, shift) step are fetched one step ahead.  (With the shift loop unrolled the compiler
+    // hoisted all nine steps' loads: 252 registers, 1.5 KB of scratch per lane.)
+    uint4 wa[4], wn[4];
+    auto load_w = [&](uint4 (&wd)[4], int step) {
+        const uint4* wf = wfrag + (size_t)step * 4 * 64 + lane;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wd[k] = wf[k * 64];
+    };
+    load_w(wa, 0);
+#pragma unroll 1
+    for (int cg = 0; cg < NCG; ++cg) {
+        f32x2_t o[2][ND];                // channels (cg 8 + half 4 + 2 pr, + 1) of candidate j
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr)
+#pragma unroll
+            for (int j = 0; j < ND; ++j) o[pr][j] = f32x2_t{0.f, 0.f};
+#pragma unroll 1
+        for (int s = 0; s < 9; ++s) {
+            load_w(wn, min(cg * 9 + s + 1, NCG * 9 - 1));
+            const int kh = s / 3, kw = s - 3 * kh;
+            const int hp = (wave + kh) * HW + l31 + kw;
+            // ---- Q[kd, 8 channels of cg] at the shifted positions: [32 rows][32 positions], K = 32 left channels ----
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const f16x8 a0 = __builtin_bit_cast(f16x8, wa[ks * 2 + 0]);
+                const f16x8 a1 = __builtin_bit_cast(f16x8, wa[ks * 2 + 1]);
+                const f16x8 b0 = __builtin_bit_cast(f16x8, ltile[(ks * 2 + half) * 2 + 0][hp]);
+                const f16x8 b1 = __builtin_bit_cast(f16x8, ltile[(ks * 2 + half) * 2 + 1][hp]);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc, 0, 0, 0);      // smallest cross terms first
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc, 0, 0, 0);
+            }
+            // ---- 27 multiply-adds per output, 9 at a time: accumulator register kd * 4 + i is row kd * 8 + half * 4 + i ----
+            const float* ap = &atile[0][0][0] + hp;
+            float av[ND + 2];            // av[1 + j] = att[j]; av[0] = av[ND + 1] = 0 (the zero planes)
+#pragma unroll
+            for (int j = -1; j <= ND; ++j) av[1 + j] = ap[j * NPOSH];
+#pragma unroll
+            for (int kd = 0; kd < 3; ++kd) {
+                const float4 u = uinv[((cg * 9 + s) * 2 + half) * 3 + kd];
+                // (two exact multiplications, the tile's scale first: the product of the two powers of two can leave fp32's range)
+                const f32x2_t v0 = {acc[kd * 4 + 0] * unl * u.x, acc[kd * 4 + 1] * unl * u.y};
+                const f32x2_t v1 = {acc[kd * 4 + 2] * unl * u.z, acc[kd * 4 + 3] * unl * u.w};
+#pragma unroll
+                for (int j = 0; j < ND; ++j) {
+                    const f32x2_t a = {av[j + kd], av[j + kd]};
+                    o[0][j] = __builtin_elementwise_fma(a, v0, o[0][j]);
+                    o[1][j] = __builtin_elementwise_fma(a, v1, o[1][j]);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) wa[k] = wn[k];
+        }
+        if (inside) {
+            float* ob = out + (((size_t)b * Cout + cg * MROWS + half * 4) * ND) * plane + (size_t)h * W + w;
+#pragma unroll
+            for (int pr = 0; pr < 2; ++pr)
+#pragma unroll
+                for (int j = 0; j < ND; ++j) {
+                    ob[((size_t)(2 * pr) * ND + j) * plane] = o[pr][j][0];
+                    ob[((size_t)(2 * pr + 1) * ND + j) * plane] = o[pr][j][1];
+                }
+        }
+    }
+}
+
+// Left-half weights [32][32][27] -> the A fragments of stem_left_mfma: two fp16 terms of w / u, u = the power of two that brings
+// the row's (one tap, one output channel: 32 left channels) largest |w| into [2^14, 2^15), and the u's behind them.  One thread
+// per fragment row (channel group, shift, row of 32); rows 24..31 are zero.
+__global__ __launch_bounds__(256) void pack_stem_left_f16s_kernel(const float* __restrict__ w, unsigned short* __restrict__ wsplit,
+                                                                   float* __restrict__ winv) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= NCG * 9 * 32) return;
+    const int row = t % 32, s = (t / 32) % 9, cg = t / (32 * 9);
+    const int kd = row / MROWS, c8 = row % MROWS;
+    const bool live = kd < 3;
+    const float* wr = w + ((size_t)(cg * MROWS + c8) * 32) * 27 + kd * 9 + s;      // + c * 27
+    float m = 0.f;
+    if (live)
+        for (int c = 0; c < 32; ++c) m = fmaxf(m, fabsf(wr[c * 27]));
+    const float u = unscale_for(max((int)(__float_as_uint(m) >> 23), E_MIN));
+    if (live) winv[((cg * 9 + s) * 2 + c8 / 4) * 12 + kd * 4 + c8 % 4] = u;
+    for (int c = 0; c < 32; ++c) {
+        const int ks = c / 16, hf = (c / 8) % 2, j = c % 8;
+        const float x = live ? wr[c * 27] / u : 0.f;                               // exact: a power of two
+#pragma unroll
+        for (int term = 0; term < 2; ++term)
+            wsplit[((((size_t)(cg * 9 + s) * 2 + ks) * 2 + term) * 64 + hf * 32 + row) * 8 + j] = split_weight_f16(x, term);
+    }
+}
+
+template <int ND>
+int launch_mfma(const float* left, const void* wsplit, const float* att, float* out, int B, int H, int W, hipStream_t st) {
+    const float4* winv = reinterpret_cast<const float4*>(reinterpret_cast<const unsigned short*>(wsplit) + WFRAG_HALVES);
+    dim3 grid(ss::ceil_div(W, FTW), ss::ceil_div(H, FTH), B);
+    hipLaunchKernelGGL(stem_left_mfma<ND>, grid, dim3(256), 0, st, left, reinterpret_cast<const uint4*>(wsplit), winv, att, out, H, W);
+    return ss::check_launch();
+}
+
+}  // namespace
+
+extern "C" int ss_stem_left_mfma_fwd(const float* left, const void* wsplit, const float* att, float* out, int B, int C,
+                                     int Cout, int nd, int H, int W, ss_stream_t stream) {
+    SS_REQUIRE(left && wsplit && att && out);
+    SS_REQUIRE(B > 0 && C > 0 && Cout > 0 && nd > 0 && H > 0 && W > 0);
+    SS_REQUIRE((reinterpret_cast<uintptr_t>(wsplit) & 15) == 0);
+    if (C != 32 || Cout != 32 || B > 65535 || ss::ceil_div(H, FTH) > 65535) return SS_ERR_UNSUPPORTED;
+    if ((long long)C * H * W * 4 >= 0x7fffffffLL || (long long)nd * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;   // 32-bit buffer offsets
+    hipStream_t st = ss::as_stream(stream);
+    if (nd == 24) return launch_mfma<24>(left, wsplit, att, out, B, H, W, st);
+    if (nd == 32) return launch_mfma<32>(left, wsplit, att, out, B, H, W, st);
+    if (nd == 6) return launch_mfma<6>(left, wsplit, att, out, B, H, W, st);
+    return SS_ERR_UNSUPPORTED;
+}
+
+extern "C" int ss_pack_stem_left_weights_f16s(const float* w, void* wsplit, int Cout, int C, ss_stream_t stream) {
+    SS_REQUIRE(w && wsplit);
+    SS_REQUIRE((reinterpret_cast<uintptr_t>(wsplit) & 15) == 0);
+    if (C != 32 || Cout != 32) return SS_ERR_UNSUPPORTED;
+    unsigned short* ws = reinterpret_cast<unsigned short*>(wsplit);
+    hipLaunchKernelGGL(pack_stem_left_f16s_kernel, dim3(ss::ceil_div(NCG * 9 * 32, 256)), dim3(256), 0, ss::as_stream(stream), w, ws,
+                       reinterpret_cast<float*>(ws + WFRAG_HALVES));
+    return ss::check_launch();
 }

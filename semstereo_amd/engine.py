@@ -759,6 +759,14 @@ CLASSIFIER_FUSED = os.environ.get("SS_CLASSIFIER_FUSED", "1") != "0"
 
 
 STEM_LEFT_FUSED = os.environ.get("SS_STEM_LEFT_FUSED", "1") != "0"     # Q of the broadcast half on the fly (one launch) or through HBM (two)
+#: f16x3 engine, C = Cout = 32, nd in {6, 24, 32}: the fused launch on two fp16 terms with Q by shifts (stem_left_mfma, Q stays in
+#: registers); 0: stem_left_fused (six bf16 products, Q through LDS) for every shape
+STEM_LEFT_MFMA = os.environ.get("SS_STEM_LEFT_MFMA", "1") != "0"
+
+
+def stem_left_takes_mfma(C, Cout, nd):
+    """the launches of stem_broadcast_half that run stem_left_mfma"""
+    return CONV_ENGINE == "f16x3" and STEM_LEFT_FUSED and STEM_LEFT_MFMA and C == 32 and Cout == 32 and nd in (6, 24, 32)
 
 
 def _stem_halves_params(stem, C):
@@ -775,8 +783,9 @@ def _stem_halves_params(stem, C):
         # fused form: per pair of output channels 64 rows, row tap*2 + c = channel 2*pair + c, rows 54-63 zero
         wf = torch.zeros(Cout // 2, 64, C, dtype=w.dtype, device=w.device)
         wf[:, :54] = wl.reshape(Cout // 2, 2, C, 27).permute(0, 3, 1, 2).reshape(Cout // 2, 54, C)
+        wm = ops.pack_stem_left_weights_f16s(wl) if CONV_ENGINE == "f16x3" and C == 32 and Cout == 32 else None
         return (pack_pointwise_weight_bf16s(wq), pack_pointwise_weight_bf16s(wf.reshape(Cout // 2 * 64, C)),
-                pack_conv_weight_bf16s(w[:, C:].contiguous(), _tiled_nterms()), sc, sh)
+                pack_conv_weight_bf16s(w[:, C:].contiguous(), _tiled_nterms()), sc, sh, wm)
     return _cache(stem).get("bc/halves/" + CONV_ENGINE, srcs, build)
 
 
@@ -787,8 +796,10 @@ def stem_broadcast_half(stem, left, att):
     assert stem.is_3d and not stem.deconv and CONV_ENGINE != "f32" and _inference(stem, left, att)
     C, Cout = left.shape[1], stem.conv.out_channels
     nterms = _aux_nterms()
-    wq, wf, _, _, _ = _stem_halves_params(stem, C)
+    wq, wf, _, _, _, wm = _stem_halves_params(stem, C)
     PATH_COUNTS["hip"] += 1
+    if stem_left_takes_mfma(C, Cout, att.shape[-3]):
+        return ops.stem_left_mfma(left, wm, att, Cout)
     if C == 32 and Cout % 2 == 0 and STEM_LEFT_FUSED:
         return ops.stem_left_fused(left, wf, att, Cout, nterms)
     q = conv3d_pointwise_bf16s_hip(left, wq, 27 * Cout, None, None, False, nterms)               # [B, 27*Cout, H, W]
@@ -800,7 +811,7 @@ def stem_volume_half(stem, right_vol, partial, gate=None):
     and the optional channelAtt gate (`gate` [B,Cout,H,W]: the SIGMOID of the gate's logits) on the total."""
     assert stem.is_3d and not stem.deconv and CONV_ENGINE != "f32" and _inference(stem, right_vol, partial, gate)
     nterms = _tiled_nterms()
-    _, _, wr, scale, shift = _stem_halves_params(stem, right_vol.shape[1])
+    _, _, wr, scale, shift, _ = _stem_halves_params(stem, right_vol.shape[1])
     g = None if gate is None else gate.contiguous()
     return conv3d_bf16s_hip(right_vol, wr, stem.conv.out_channels, scale, shift, bool(stem.relu), nterms, None, g, partial=partial)
 
@@ -822,7 +833,7 @@ def stem_volume_half_presplit(stem, xs, xexp, partial, gate=None):
     """stem_volume_half on the pre-split warped half (xs, xexp of ops.concat_volume_sampled_presplit)."""
     assert stem.is_3d and not stem.deconv and CONV_ENGINE == "f16x3" and _inference(stem, partial, gate)
     B, nchunks, _, D, H, W, _ = xs.shape
-    _, _, wr, scale, shift = _stem_halves_params(stem, nchunks * 8)
+    _, _, wr, scale, shift, _ = _stem_halves_params(stem, nchunks * 8)
     Cout = stem.conv.out_channels
     g = None if gate is None else gate.contiguous()
     dev = _lib.require_device(partial, scale, shift, g)
@@ -863,7 +874,7 @@ def stem_gather_half(stem, right, samples, att, partial, gate=None, consume_part
     B, C, H, W = right.shape
     nd = samples.shape[1]
     assert samples.shape == (B, nd, H, W) and att.shape == samples.shape
-    _, _, wr, scale, shift = _stem_halves_params(stem, C)
+    _, _, wr, scale, shift, _ = _stem_halves_params(stem, C)
     Cout = stem.conv.out_channels
     g = None if gate is None else gate.contiguous()
     dev = _lib.require_device(right, samples, att, partial, scale, shift, g)
@@ -893,4 +904,4 @@ ATTENTION_FORM = os.environ.get("SS_ATTENTION", "split")      # "split" (3 launc
 
 #: the names tests / tools may SET on this module; `modules.X` forwards reads of them here
 SWITCHES = ("CONV_ENGINE", "DECONV_F16", "DECONV_MIN_WORKGROUPS", "DECONV_BF16S", "CLASSIFIER_CL", "CLASSIFIER_FUSED", "CLASSIFIER_FOLD", "TRAIN_HIP", "SSR_TRAIN_HIP", "LOSS_HIP", "METRICS_HIP", "ATTENTION_FORM",
-            "STEM_LEFT_FUSED", "STEM_PRESPLIT", "STEM_GATHER", "STEM_INPLACE", "HEAD_F16", "CONV2D_HIP", "DECODER_HIP", "HEADS_HIP")
+            "STEM_LEFT_FUSED", "STEM_LEFT_MFMA", "STEM_PRESPLIT", "STEM_GATHER", "STEM_INPLACE", "HEAD_F16", "CONV2D_HIP", "DECODER_HIP", "HEADS_HIP")

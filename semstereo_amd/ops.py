@@ -517,6 +517,35 @@ def stem_left_fused(left, wsplit, att, Cout, nterms=6):
     return out
 
 
+#: int16 elements of ss_pack_stem_left_weights_f16s' result: 4 channel groups x 9 shifts x 2 K-steps x 2 terms x 64 lanes x 8 fp16,
+#: then the 4 x 9 x 24 inverse scales as floats
+STEM_LEFT_MFMA_PACKED = 4 * 9 * 2 * 2 * 64 * 8 + 2 * 4 * 9 * 24
+
+
+def pack_stem_left_weights_f16s(wl):
+    """Left-half weights [32, 32, 27] fp32 -> the fragments of stem_left_mfma (int16 tensor, 16-B aligned)."""
+    wl = _c(wl.detach().float())
+    dev = _lib.require_device(wl)
+    assert tuple(wl.shape) == (32, 32, 27)
+    out = torch.empty(STEM_LEFT_MFMA_PACKED, dtype=torch.int16, device=wl.device)
+    with torch.cuda.device(dev):
+        call("ss_pack_stem_left_weights_f16s", ptr(wl), ptr(out), 32, 32)
+    return out
+
+
+def stem_left_mfma(left, wsplit, att, Cout):
+    """stem_left_fused on two fp16 terms with Q by shifts (stem_left.hip, stem_left_mfma): left [B,32,H,W], wsplit =
+    pack_stem_left_weights_f16s, att [B,1,nd,H,W] or [B,nd,H,W] -> [B,32,nd,H,W].  C = Cout = 32, nd in {6, 24, 32}."""
+    left = _c(left)
+    att = _c(att.reshape(att.shape[0], att.shape[-3], att.shape[-2], att.shape[-1]))
+    dev = _lib.require_device(left, att)
+    B, nd, H, W = att.shape
+    out = torch.empty((B, Cout, nd, H, W), dtype=left.dtype, device=left.device)
+    with torch.cuda.device(dev):
+        call("ss_stem_left_mfma_fwd", ptr(left), ptr(wsplit), ptr(att), ptr(out), B, left.shape[1], Cout, nd, H, W)
+    return out
+
+
 def warp_correlation(x, y, disparity_samples):
     """Fused models/SemStereo.py:291-292: mean over channels of x * warp(y) -> [B, nd, H, W].
     Inference only."""

@@ -2,7 +2,7 @@
 """Runs ONE kernel of the path back to back (live shapes of the 1024 x 1024 / maxdisp 128 pair) so that rocprofv3 kernel-trace /
 PMC passes see nothing else, and prints its time and algorithmic-byte rate.
 usage: run_kernel.py <kernel> [batch] [iters]        kernels: gwc gwc_fused patch head head_att classif classif_cl classif_plain classif_att head_cl conv_s1_cl conv_mid conv_low conv_mid_att conv_low_att attn attn_att warp ssr ssr2048 strength topk
-                                                               catt8 catt4 upsoft stem_left stem stem_gather stem_gather_smooth conv_s1 conv_s2 conv_s2_att deconv deconv5 deconv_att6 deconv_att5"""
+                                                               catt8 catt4 upsoft stem_left stem_left_mfma stem_left2048 stem_left_mfma2048 stem stem_gather stem_gather_smooth conv_s1 conv_s2 conv_s2_att deconv deconv5 deconv_att6 deconv_att5"""
 import os
 import sys
 import time
@@ -76,11 +76,13 @@ elif name == "upsoft":
     coarse = R(B, 1, 32, 128, 128)
     fn = lambda: O.upsample_softmax_regression(coarse, 32, 256, 256)           # noqa: E731
     nbytes = 4.0 * B * (32 * 128 * 128 + 66 * 256 * 256)
-elif name == "stem_left":
+elif name in ("stem_left", "stem_left_mfma", "stem_left2048", "stem_left_mfma2048"):   # stem_left_fused (six bf16 products, Q through LDS) / stem_left_mfma (two fp16 terms, Q by shifts); ...2048: the 2048 x 2048 pair
+    sa.engine.STEM_LEFT_MFMA = name.startswith("stem_left_mfma")
+    hq = 512 if name.endswith("2048") else 256
     stem = M.BasicConv(64, 32, is_3d=True, kernel_size=3, stride=1, padding=1).to(dev).eval()
-    cl, att = R(B, 32, 256, 256), torch.rand(B, 1, 24, 256, 256, device=dev)
+    cl, att = R(B, 32, hq, hq), torch.rand(B, 1, 24, hq, hq, device=dev)
     fn = lambda: M.stem_broadcast_half(stem, cl, att)                          # noqa: E731
-    nbytes = 4.0 * B * (32 + 24 + 32 * 24) * 256 * 256
+    nbytes = 4.0 * B * (32 + 24 + 32 * 24) * hq * hq
 elif name in ("attn", "attn_att"):       # attention_block of hourglass2 ([128,6,64,64], windows 6x4x4) / of the attention-branch hourglass ([128,8,32,32], 4x4x4)
     blk, d, hw = ((6, 4, 4), 6, 64) if name == "attn" else ((4, 4, 4), 8, 32)
     ab = M.attention_block(128, 16, blk).to(dev).eval()
