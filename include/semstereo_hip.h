@@ -403,6 +403,20 @@ int ss_pack_seghead_weights_f16s(const float* w, void* wsplit, int Cin, ss_strea
 /* F.interpolate(in, size=(2H, 2W), mode="bilinear", align_corners=False) of [B,C,H,W] -> [B,C,2H,2W] (segmenthead.forward with
  * scale_factor 2, models/submodule.py:46-51): weights 0.25 / 0.75, source index clamped at the borders, horizontal pair first. */
 int ss_bilinear_up2_fwd(const float* in, float* out, int B, int C, int H, int W, ss_stream_t stream);
+/* (training) The head's tail under autograd (csrc/seghead_train.hip): out = up2(w2 . a + bias) in one pass, the low-resolution logits
+ * never written.  a [B,K,H,W]: the head's 32-channel map after BatchNorm + ReLU; w2 [C,K], bias [C]: conv2's parameters; out
+ * [B,C,sH,sW], s = 1 + up2; up2 = 1: F.interpolate(size=(2H, 2W), mode="bilinear", align_corners=False) with the arithmetic of
+ * ss_bilinear_up2_fwd, up2 = 0 (scale_factor None): the 1x1 + bias alone.  K = 32 and C <= 8 (SS_ERR_UNSUPPORTED otherwise, and for
+ * one element's `a` or `out` of 2 GiB or more).  The tile is 8 x 32 positions of one element whatever the batch. */
+int ss_seghead_tail_fwd(const float* a, const float* w2, const float* bias, float* out, int B, int K, int C, int H, int W, int up2,
+                        ss_stream_t stream);
+/* Its backward in one pass over grad_out [B,C,sH,sW]: g = the adjoint of the up-sampling (G read at the clamped index), then
+ * grad_a [B,K,H,W] = w2^T g, grad_w2 [C,K] = sum g a, grad_bias [C] = sum g.  Any of the three may be NULL (not computed), not all.
+ * The two sums go through one partial per workgroup in `workspace` (ss_seghead_tail_workspace_bytes; may be NULL when both are) and a
+ * fixed-order final sum in double: no floating-point atomics, the same inputs give the same bits. */
+int ss_seghead_tail_bwd(const float* grad_out, const float* a, const float* w2, float* grad_a, float* grad_w2, float* grad_bias,
+                        float* workspace, int B, int K, int C, int H, int W, int up2, ss_stream_t stream);
+int ss_seghead_tail_workspace_bytes(int B, int K, int C, int H, int W, long long* bytes);
 /* two-term fp16 form of the 2-D weights (nterms = 19 of ss_conv2d_bf16s_fwd; see ss_pack_conv3d_weights_f16s):
  * ceil(Cin/8)*5*2*2*Cout*16 + 4*Cout bytes. */
 int ss_pack_conv2d_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);

@@ -70,6 +70,8 @@ _SIGNATURES = {
     "ss_seghead_logits_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "ss_pack_seghead_weights_f16s": [_P, _P, _I, _P],
     "ss_bilinear_up2_fwd": [_P, _P, _I, _I, _I, _I, _P],
+    "ss_seghead_tail_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "ss_seghead_tail_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "ss_conv3d_head_bf16s_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "ss_conv3d_head_bf16s_cl_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "ss_conv3d_bf16s_cl_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -123,7 +125,7 @@ _SIGNATURES = {
     "ss_seg_confusion_fwd": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_longlong, ctypes.c_longlong, _P, _I, _P, ctypes.c_longlong, _P],
 }
 EXPORTS = sorted(list(_SIGNATURES) + ["ss_abi_version", "ss_status_string", "ss_last_hip_error", "ss_ssr_param_count", "ss_reload_tuning",
-                                           "ss_set_fill_hint", "ss_get_fill_hint"])
+                                           "ss_set_fill_hint", "ss_get_fill_hint", "ss_seghead_tail_workspace_bytes"])
 
 _lib = None
 
@@ -152,6 +154,8 @@ def load():
     lib.ss_set_fill_hint.argtypes = [_I]
     lib.ss_get_fill_hint.restype = _I
     lib.ss_get_fill_hint.argtypes = []
+    lib.ss_seghead_tail_workspace_bytes.restype = _I   # (no stream argument: bound apart from _SIGNATURES)
+    lib.ss_seghead_tail_workspace_bytes.argtypes = [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]
     if lib.ss_abi_version() != ABI_VERSION:
         raise SemStereoHipError(f"ABI mismatch: library {lib.ss_abi_version()} != binding {ABI_VERSION}; rebuild")
     for name, argtypes in _SIGNATURES.items():

@@ -30,6 +30,7 @@ from . import _lib, ops
 from . import deferred as dfr
 from . import engine as E
 from . import train as T
+from . import train_heads as TH
 from . import train_ssr as TS
 from ._lib import call, ptr
 # the functional layer (engine.py) and the training convolutions (train_layers.py) under their historical names: `modules.X`
@@ -943,8 +944,9 @@ class segmenthead(nn.Module):
     """segmenthead (models/submodule.py:31-52): BasicConv(3x3) -> Conv2d(1x1, bias) -> bilinear up-sampling by `scale_factor`; keys
     `conv1.conv.weight`, `conv1.bn.*`, `conv2.weight`, `conv2.bias`.  Inference with interplanes == 32, at most 8 classes, a channel
     count that is a multiple of 8 and scale_factor 2 or None runs ss_seghead_logits_fwd (the 32-channel map never leaves the
-    accumulators) and ss_bilinear_up2_fwd; everything else (training, autograd, CPU, float64, another engine, SS_HEADS_HIP=0, other
-    widths or factors) runs the reference's own statements on the stock layers.  Where deferred handles are in use the call hands
+    accumulators) and ss_bilinear_up2_fwd; with SS_HEADS_TRAIN_HIP=1 training and autograd run train_heads.seghead_train; everything
+    else (training and autograd by default, CPU, float64, another engine, SS_HEADS_HIP=0, other widths or factors) runs the
+    reference's own statements on the stock layers.  Where deferred handles are in use the call hands
     out a handle, so a result nobody reads -- `pred_label_r` of an eval forward, models/SemStereo.py:255 vs :346 -- is never
     launched."""
 
@@ -985,6 +987,8 @@ class segmenthead(nn.Module):
             if y is not None:
                 PATH_COUNTS["hip"] += 1
                 return y
+        elif TH.seghead_train_applies(self, x):                 # (SS_HEADS_TRAIN_HIP=1: autograd / train() on the HIP kernels)
+            return TH.seghead_train(self, x)
         # the reference's own statements, models/submodule.py:42-52
         x = _stock_basicconv(self.conv1, x)
         out = self.conv2(x)
@@ -998,8 +1002,9 @@ class segmenthead(nn.Module):
 class ChalProjection(nn.Sequential):
     """`chal_0 .. chal_4` (models/SemStereo.py:213-217): nn.Sequential(nn.Conv2d(Cin, Cout, 1), nn.BatchNorm2d(Cout)); keys `0.*`,
     `1.*`.  Inference: ss_conv2d_k1_f16s_fwd with the bias and the BatchNorm folded into the epilogue; `forward_pair` sends the left
-    and the right view (chal_1 / chal_2, :259-260, 264-265) through one launch.  Training, autograd, CPU, float64, another engine,
-    SS_HEADS_HIP=0 or a channel count that is no multiple of 8: the stock layers."""
+    and the right view (chal_1 / chal_2, :259-260, 264-265) through one launch.  With SS_HEADS_TRAIN_HIP=1 training and autograd run
+    train_heads.proj_train.  Training and autograd by default, CPU, float64, another engine, SS_HEADS_HIP=0 or a channel count that is
+    no multiple of 8: the stock layers."""
 
     def __init__(self, in_channels, out_channels):
         super().__init__(nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=1), nn.BatchNorm2d(out_channels))
@@ -1025,10 +1030,13 @@ class ChalProjection(nn.Sequential):
 
     def forward(self, x):
         x = dfr.real(x)
-        y = self._hip(x)
-        if y is not None:
-            PATH_COUNTS["hip"] += 1
-            return y
+        if isinstance(x, torch.Tensor) and x.is_cuda and _inference(self, x):
+            y = E.run_conv2d_k1(self, "chal", self[0], self[1], x, False)
+            if y is not None:
+                PATH_COUNTS["hip"] += 1
+                return y
+        elif TH.proj_train_applies(self, x):                    # (SS_HEADS_TRAIN_HIP=1: autograd / train() on the HIP kernels)
+            return TH.proj_train(self, x)
         PATH_COUNTS["torch"] += 1
         return self[1](self[0](x))
 
