@@ -373,6 +373,30 @@ int ss_deconv2d_bf16s_pair_fwd(const float* in_a, const float* in_b, const void*
  * channel by a power of two, + float[32 ceil(Cout/32)] of the inverse scales:
  * ceil(Cin/8) * ceil(Cout/32) * 16384 + 128 * ceil(Cout/32) bytes, 16-byte aligned. */
 int ss_pack_deconv2d_weights_f16s(const float* w, void* wsplit, int Cin, int Cout, ss_stream_t stream);
+/* (training) The data gradient of ConvTranspose2d(k = 4, s = 2, p = 1) -- conv1 of every 2-D Conv2x (models/submodule.py:104,
+ * 136-138, 150) and `spx2` (models/SemStereo.py:207) -- as what it is: Conv2d(Cin, Cout, 4, stride=2, padding=1, bias=False) on
+ * in [B,Cin,H,W] (the gradient of the transposed conv's output; H and W even, else SS_ERR_UNSUPPORTED) -> out [B,Cout,H/2,W/2], the
+ * transposed conv's own weight tensor read as [Cout,Cin,4,4] (no flip).  Two-term fp16 form of the matrix-core engine
+ * (csrc/deconv2d_train.hip); no affine, no ReLU.  The tile is chosen per layer: an element has the same bits alone and in a batch.
+ * An infinity in `in` reaches its own receptive field only.  wsplit from ss_pack_conv2d_k4s2_weights_f16s.  One element's input or
+ * output of 2 GiB or more: SS_ERR_UNSUPPORTED. */
+int ss_conv2d_k4s2_f16s_fwd(const float* in, const void* wsplit, float* out, int B, int Cin, int H, int W, int Cout, ss_stream_t stream);
+/* Conv2d weight [Cout,Cin,4,4] fp32 (= nn.ConvTranspose2d's [its Cin, its Cout, 4, 4], models/submodule.py:104) -> the fragments of
+ * ss_conv2d_k4s2_f16s_fwd: [ceil(Cin/8)][ceil(Cout/32)][8 K-steps][2 terms][2 lane halves][32 channels][8] fp16 of w scaled per output
+ * channel by a power of two, + float[32 ceil(Cout/32)] of the inverse scales:
+ * ceil(Cin/8) * ceil(Cout/32) * 16384 + 128 * ceil(Cout/32) bytes, 16-byte aligned. */
+int ss_pack_conv2d_k4s2_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);
+/* (training) The weight gradient of the same layer (models/submodule.py:104, 136-138, 150; models/SemStereo.py:207):
+ * grad_w[ci,co,kh,kw] = sum_{b,y,x} in[b,ci,y,x] * grad_out[b,co,2y-1+kh,2x-1+kw], in [B,Cin,H,W], grad_out [B,Cout,2H,2W], grad_w
+ * [Cin,Cout,4,4].  Three-term bf16 form, six products, fp32 accumulation; one partial [16][32][32] block per workgroup in `workspace`
+ * (ss_deconv2d_k4s2_wgrad_workspace_bytes) and a fixed-order final sum in double: no floating-point atomics, the same inputs give
+ * the same bits.  One element's tensors of 2 GiB or more: SS_ERR_UNSUPPORTED. */
+int ss_deconv2d_k4s2_wgrad_fwd(const float* in, const float* grad_out, float* grad_w, float* workspace, int B, int Cin, int H, int W,
+                               int Cout, ss_stream_t stream);
+/* Its workspace: nparts * ceil(Cin/32) * ceil(Cout/32) * 65536 bytes, where with rows = B * H and tiles = ceil(Cin/32) * ceil(Cout/32)
+ * a partial covers rpp = min(rows, max(ceil(rows / clamp(1024 / tiles, 1, 256)), ceil(2048 / W))) rows and nparts = ceil(rows / rpp):
+ * at most max(64 MiB, tiles * 64 KiB) -- 64 MiB up to 1024 weight tiles, one partial per tile beyond.  A refused call writes nothing. */
+int ss_deconv2d_k4s2_wgrad_workspace_bytes(int B, int Cin, int H, int W, int Cout, long long* bytes);
 /* Conv2d(Cin, Cout, 1) + per-channel affine + optional ReLU on [B,Cin,npos] maps (npos = H*W) -> out [B,Cout,npos]: the projections
  * `chal_0 .. chal_4` = nn.Sequential(nn.Conv2d(1x1, bias), nn.BatchNorm2d) (models/SemStereo.py:213-217, called at :258-262), with
  * the bias and the eval BatchNorm folded into (scale, shift), on the two-term fp16 form of the matrix-core engine with a loop over

@@ -753,6 +753,10 @@ SSR_TRAIN_HIP = os.environ.get("SS_SSR_TRAIN_HIP", "1") != "0"     # 0: SSR_upsa
 #: 1: the segmentation heads and the chal_* projections run train_heads.py (HIP forward and backward) under autograd / in train();
 #: off by default: the twins of `accelerate(model, heads=True)` then keep the stock layers there (needs TRAIN_HIP and the heads' own switch)
 HEADS_TRAIN_HIP = os.environ.get("SS_HEADS_TRAIN_HIP", "0") != "0"
+#: 1: the 2-D decoder -- every Conv2x of FeatUp and of the spx chain, and spx2 -- runs train_decoder.py (HIP forward and backward) under
+#: autograd / in train(); off by default: the twins of `accelerate(model, decoder=True)` then keep the stock layers there (needs TRAIN_HIP,
+#: the decoder's own switch and the f16x3 engine)
+DECODER_TRAIN_HIP = os.environ.get("SS_DECODER_TRAIN_HIP", "0") != "0"
 LOSS_HIP = os.environ.get("SS_LOSS_HIP", "1") != "0"      # 0: semstereo_amd.losses keeps its PyTorch composition (no boolean indexing) on the GPU too
 METRICS_HIP = os.environ.get("SS_METRICS_HIP", "1") != "0"      # 0: semstereo_amd.metrics keeps its PyTorch composition (no boolean indexing, no .cpu()) on the GPU too
 CLASSIFIER_CL = os.environ.get("SS_CLASSIFIER_CL", "1") != "0"    # 0: plain-layout intermediate inside the classifiers (two generic launches)
@@ -906,5 +910,5 @@ def stem_of_broadcast_and_volume(stem, left, att, right_vol, gate=None):
 ATTENTION_FORM = os.environ.get("SS_ATTENTION", "split")      # "split" (3 launches) | "fused" (one kernel per window)
 
 #: the names tests / tools may SET on this module; `modules.X` forwards reads of them here
-SWITCHES = ("CONV_ENGINE", "DECONV_F16", "DECONV_MIN_WORKGROUPS", "DECONV_BF16S", "CLASSIFIER_CL", "CLASSIFIER_FUSED", "CLASSIFIER_FOLD", "TRAIN_HIP", "SSR_TRAIN_HIP", "HEADS_TRAIN_HIP", "LOSS_HIP", "METRICS_HIP", "ATTENTION_FORM",
+SWITCHES = ("CONV_ENGINE", "DECONV_F16", "DECONV_MIN_WORKGROUPS", "DECONV_BF16S", "CLASSIFIER_CL", "CLASSIFIER_FUSED", "CLASSIFIER_FOLD", "TRAIN_HIP", "SSR_TRAIN_HIP", "HEADS_TRAIN_HIP", "DECODER_TRAIN_HIP", "LOSS_HIP", "METRICS_HIP", "ATTENTION_FORM",
             "STEM_LEFT_FUSED", "STEM_LEFT_MFMA", "STEM_PRESPLIT", "STEM_GATHER", "STEM_INPLACE", "HEAD_F16", "CONV2D_HIP", "DECODER_HIP", "HEADS_HIP")

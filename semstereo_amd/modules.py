@@ -30,6 +30,7 @@ from . import _lib, ops
 from . import deferred as dfr
 from . import engine as E
 from . import train as T
+from . import train_decoder as TD
 from . import train_heads as TH
 from . import train_ssr as TS
 from ._lib import call, ptr
@@ -788,7 +789,8 @@ class Conv2x(nn.Module):
     BasicConv(3x3); keys `conv1.conv.weight`, `conv1.bn.*`, `conv2.conv.weight`, `conv2.bn.*`.  Inference of the 2-D transposed,
     concatenating form with matching shapes -- every Conv2x of FeatUp and of the spx chain -- runs the 4x4 stride-2 transposed
     kernel and the concat-free 3x3 (no torch.cat); everything else (autograd, CPU, the 3-D form, concat=False, keep_dispc, a skip
-    map of another size, the f32 engine, SS_DECODER_HIP=0) runs the reference's own statements on the stock layers."""
+    map of another size, the f32 engine, SS_DECODER_HIP=0) runs the reference's own statements on the stock layers -- except that with
+    SS_DECODER_TRAIN_HIP=1 autograd and train() calls of the same form run train_decoder.conv2x_train (HIP forward and backward)."""
 
     def __init__(self, in_channels, out_channels, deconv=False, is_3d=False, concat=True, keep_concat=True, bn=True, relu=True, keep_dispc=False):
         super().__init__()
@@ -850,6 +852,9 @@ class Conv2x(nn.Module):
             if y is not None:
                 PATH_COUNTS["hip"] += 1                        # (one per Conv2x on this path; the stock path counts one per BasicConv)
                 return self._conv2_after_hip_deconv(y, rem)[0]
+        if (not _inference(self, x, rem) and isinstance(x, torch.Tensor) and isinstance(rem, torch.Tensor)
+                and TD.conv2x_train_applies(self, x, rem)):     # (SS_DECODER_TRAIN_HIP=1: autograd / train() on the HIP kernels)
+            return TD.conv2x_train(self, x, rem)
         # the reference's own statements, models/submodule.py:149-161
         x = _stock_basicconv(a, x)
         if x.shape != rem.shape:
@@ -880,7 +885,9 @@ class Conv2x(nn.Module):
 
 class FeatUp(nn.Module):
     """FeatUp (models/SemStereo.py:59-86): four Conv2x up the backbone's pyramid, each applied to the left and to the right view; keys
-    `deconv32_16.*`, `deconv16_8.*`, `deconv8_4.*`, `deconv4_2.*`.  Both views of a layer go through one launch (Conv2x.forward_pair)."""
+    `deconv32_16.*`, `deconv16_8.*`, `deconv8_4.*`, `deconv4_2.*`.  In inference both views of a layer go through one launch
+    (Conv2x.forward_pair).  With SS_DECODER_TRAIN_HIP=1, autograd and train() calls run each layer on the left view and then on the right
+    one, as the reference does: every call has its own batch statistics."""
 
     def __init__(self):
         super().__init__()
@@ -903,6 +910,14 @@ class FeatUp(nn.Module):
     def forward(self, featL, featR=None):
         x2, x4, x8, x16, x32 = featL
         y2, y4, y8, y16, y32 = featR
+        if E.DECODER_TRAIN_HIP and not _inference(self, *(dfr.real(t) for t in (*featL, *featR))):
+            # autograd / train(): each Conv2x on the left view, then on the right one, as the reference calls them (:74-84) -- each call
+            # has its own batch statistics and moves the running ones, so the views are never paired here
+            x16, y16 = self.deconv32_16(x32, x16), self.deconv32_16(y32, y16)
+            x8, y8 = self.deconv16_8(x16, x8), self.deconv16_8(y16, y8)
+            x4, y4 = self.deconv8_4(x8, x4), self.deconv8_4(y8, y4)
+            x2, y2 = self.deconv4_2(x4, x2), self.deconv4_2(y4, y2)
+            return [x2, x4, x8, x16, x32], [y2, y4, y8, y16, y32]
         x16, y16 = self.deconv32_16.forward_pair(x32, x16, y32, y16)
         x8, y8 = self.deconv16_8.forward_pair(x16, x8, y16, y8)
         x4, y4 = self.deconv8_4.forward_pair(x8, x4, y8, y4)
@@ -932,6 +947,8 @@ class Spx2(nn.Sequential):
             if y is not None:
                 PATH_COUNTS["hip"] += 1
                 return y
+        elif isinstance(x, torch.Tensor) and TD.spx2_train_applies(self, x):     # (SS_DECODER_TRAIN_HIP=1: autograd / train())
+            return TD.spx2_train(self, x)
         PATH_COUNTS["torch"] += 1
         return self[0](x)
 
