@@ -397,6 +397,23 @@ int ss_deconv2d_k4s2_wgrad_fwd(const float* in, const float* grad_out, float* gr
  * a partial covers rpp = min(rows, max(ceil(rows / clamp(1024 / tiles, 1, 256)), ceil(2048 / W))) rows and nparts = ceil(rows / rpp):
  * at most max(64 MiB, tiles * 64 KiB) -- 64 MiB up to 1024 weight tiles, one partial per tile beyond.  A refused call writes nothing. */
 int ss_deconv2d_k4s2_wgrad_workspace_bytes(int B, int Cin, int H, int W, int Cout, long long* bytes);
+/* (training) The weight gradient of Conv2d(C0 + C1, Cout, 3, stride 1, padding 1, bias=False) applied to cat((in0, in1), 1), the
+ * concatenation never formed -- conv2 of every 2-D Conv2x (models/submodule.py:142, 157-160), `concat_feature`
+ * (models/SemStereo.py:221-223) and the 3x3 conv1 of `segmenthead` (the class whose forward is models/submodule.py:40-52):
+ * grad_w[co,ci,kh,kw] = sum_{b,y,x} grad_out[b,co,y,x] * in[b,ci,y+kh-1,x+kw-1] with zero padding; grad_out [B,Cout,H,W], in0
+ * [B,C0,H,W], in1 [B,C1,H,W]; channels ci < C0 are read from in0, the rest from in1; grad_w [Cout,C0+C1,3,3] is written whole, never
+ * accumulated into.  C1 == 0 with in1 == NULL is the single-source form (C1 > 0 with in1 == NULL, C1 < 0: SS_ERR_INVALID).  Three-term
+ * bf16 form, six products, fp32 accumulation (the arithmetic and order of ss_deconv2d_k4s2_wgrad_fwd); operands staged through LDS
+ * and split once, the grad_out row shared by the three kh waves, each input row staged once per workgroup; one partial [9][32][32]
+ * block per workgroup in `workspace` (ss_conv2d_k3_wgrad_workspace_bytes) and a fixed-order final sum in double: no floating-point
+ * atomics, the same inputs give the same bits.  One element's grad_out, in0 or in1 of 2 GiB or more, B * H beyond an int, more than
+ * 65535 weight tiles: SS_ERR_UNSUPPORTED. */
+int ss_conv2d_k3_wgrad_fwd(const float* grad_out, const float* in0, const float* in1, float* grad_w, float* workspace, int B, int C0,
+                           int C1, int H, int W, int Cout, ss_stream_t stream);
+/* Its workspace: nparts * tiles * 36864 bytes, where with rows = B * H and tiles = (ceil(C0/32) + ceil(C1/32)) * ceil(Cout/32) a
+ * partial covers rpp = min(rows, max(ceil(rows / clamp(1024 / tiles, 1, 256)), ceil(2048 / W))) rows and nparts = ceil(rows / rpp):
+ * at most max(36 MiB, tiles * 36 KiB).  A refused call writes nothing. */
+int ss_conv2d_k3_wgrad_workspace_bytes(int B, int C0, int C1, int H, int W, int Cout, long long* bytes);
 /* Conv2d(Cin, Cout, 1) + per-channel affine + optional ReLU on [B,Cin,npos] maps (npos = H*W) -> out [B,Cout,npos]: the projections
  * `chal_0 .. chal_4` = nn.Sequential(nn.Conv2d(1x1, bias), nn.BatchNorm2d) (models/SemStereo.py:213-217, called at :258-262), with
  * the bias and the eval BatchNorm folded into (scale, shift), on the two-term fp16 form of the matrix-core engine with a loop over

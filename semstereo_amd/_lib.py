@@ -67,6 +67,7 @@ _SIGNATURES = {
     "ss_conv2d_k4s2_f16s_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "ss_pack_conv2d_k4s2_weights_f16s": [_P, _P, _I, _I, _P],
     "ss_deconv2d_k4s2_wgrad_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "ss_conv2d_k3_wgrad_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "ss_conv2d_k1_f16s_fwd": [_P, _P, _P, _P, _P, _I, _I, ctypes.c_longlong, _I, _I, _P],
     "ss_conv2d_k1_f16s_pair_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_longlong, _I, _I, _P],
     "ss_pack_conv2d_k1_weights_f16s": [_P, _P, _I, _I, _P],
@@ -128,7 +129,8 @@ _SIGNATURES = {
     "ss_seg_confusion_fwd": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_longlong, ctypes.c_longlong, _P, _I, _P, ctypes.c_longlong, _P],
 }
 EXPORTS = sorted(list(_SIGNATURES) + ["ss_abi_version", "ss_status_string", "ss_last_hip_error", "ss_ssr_param_count", "ss_reload_tuning",
-                                           "ss_set_fill_hint", "ss_get_fill_hint", "ss_seghead_tail_workspace_bytes", "ss_deconv2d_k4s2_wgrad_workspace_bytes"])
+                                           "ss_set_fill_hint", "ss_get_fill_hint", "ss_seghead_tail_workspace_bytes", "ss_deconv2d_k4s2_wgrad_workspace_bytes",
+                                           "ss_conv2d_k3_wgrad_workspace_bytes"])
 
 _lib = None
 
@@ -161,6 +163,8 @@ def load():
     lib.ss_seghead_tail_workspace_bytes.argtypes = [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]
     lib.ss_deconv2d_k4s2_wgrad_workspace_bytes.restype = _I
     lib.ss_deconv2d_k4s2_wgrad_workspace_bytes.argtypes = [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]
+    lib.ss_conv2d_k3_wgrad_workspace_bytes.restype = _I
+    lib.ss_conv2d_k3_wgrad_workspace_bytes.argtypes = [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]
     if lib.ss_abi_version() != ABI_VERSION:
         raise SemStereoHipError(f"ABI mismatch: library {lib.ss_abi_version()} != binding {ABI_VERSION}; rebuild")
     for name, argtypes in _SIGNATURES.items():

@@ -757,6 +757,10 @@ HEADS_TRAIN_HIP = os.environ.get("SS_HEADS_TRAIN_HIP", "0") != "0"
 #: autograd / in train(); off by default: the twins of `accelerate(model, decoder=True)` then keep the stock layers there (needs TRAIN_HIP,
 #: the decoder's own switch and the f16x3 engine)
 DECODER_TRAIN_HIP = os.environ.get("SS_DECODER_TRAIN_HIP", "0") != "0"
+#: 1: the 3x3 weight gradients of train._Conv2dK3 (concat_feature, segmenthead.conv1) and train_decoder._Conv2dK3Cat (Conv2x.conv2) come
+#: from ss_conv2d_k3_wgrad_fwd (csrc/conv2d_wgrad.hip: one call for both sources, no atomics) instead of the 3x3x3 kernel on depth-1
+#: volumes; off by default: it changes the bits of those gradients.  Read at each call.
+CONV2D_WGRAD_HIP = os.environ.get("SS_CONV2D_WGRAD_HIP", "0") != "0"
 LOSS_HIP = os.environ.get("SS_LOSS_HIP", "1") != "0"      # 0: semstereo_amd.losses keeps its PyTorch composition (no boolean indexing) on the GPU too
 METRICS_HIP = os.environ.get("SS_METRICS_HIP", "1") != "0"      # 0: semstereo_amd.metrics keeps its PyTorch composition (no boolean indexing, no .cpu()) on the GPU too
 CLASSIFIER_CL = os.environ.get("SS_CLASSIFIER_CL", "1") != "0"    # 0: plain-layout intermediate inside the classifiers (two generic launches)
@@ -910,5 +914,5 @@ def stem_of_broadcast_and_volume(stem, left, att, right_vol, gate=None):
 ATTENTION_FORM = os.environ.get("SS_ATTENTION", "split")      # "split" (3 launches) | "fused" (one kernel per window)
 
 #: the names tests / tools may SET on this module; `modules.X` forwards reads of them here
-SWITCHES = ("CONV_ENGINE", "DECONV_F16", "DECONV_MIN_WORKGROUPS", "DECONV_BF16S", "CLASSIFIER_CL", "CLASSIFIER_FUSED", "CLASSIFIER_FOLD", "TRAIN_HIP", "SSR_TRAIN_HIP", "HEADS_TRAIN_HIP", "DECODER_TRAIN_HIP", "LOSS_HIP", "METRICS_HIP", "ATTENTION_FORM",
+SWITCHES = ("CONV_ENGINE", "DECONV_F16", "DECONV_MIN_WORKGROUPS", "DECONV_BF16S", "CLASSIFIER_CL", "CLASSIFIER_FUSED", "CLASSIFIER_FOLD", "TRAIN_HIP", "SSR_TRAIN_HIP", "HEADS_TRAIN_HIP", "DECODER_TRAIN_HIP", "CONV2D_WGRAD_HIP", "LOSS_HIP", "METRICS_HIP", "ATTENTION_FORM",
             "STEM_LEFT_FUSED", "STEM_LEFT_MFMA", "STEM_PRESPLIT", "STEM_GATHER", "STEM_INPLACE", "HEAD_F16", "CONV2D_HIP", "DECODER_HIP", "HEADS_HIP")

@@ -6,6 +6,7 @@ kernels, for what the 3x3x3 conv / transposed-conv functions of modules.py (`_Co
   conv_k1              1x1(x1) convolutions with optional bias                    redir1/2, attention_block.qkv_3d / final1x1,
                                                                                   channelAtt.im_att
   conv2d_k3            3x3 Conv2d                                                 concat_feature
+  conv2d_k3_wgrad_hip  its weight gradient on one or two sources, no atomics      opt-in (engine.CONV2D_WGRAD_HIP): conv2d_k3, Conv2x.conv2
   depthwise_patch      the depthwise (1,3,3) `patch` Conv3d                       models/SemStereo.py:219
   channel_gate         sigmoid(att)[:, :, None] * cv                              channelAtt, models/SemStereo.py:101-102
   window_attention     the windowed attention core                                models/submodule_other.py:805-834
@@ -226,6 +227,49 @@ def is_k1(conv):
 
 # ---- 3x3 Conv2d (concat_feature) ----------------------------------------------------------------------------------------------
 
+def conv2d_k3_wgrad_applies(g, x, rem=None):
+    """engine.CONV2D_WGRAD_HIP (SS_CONV2D_WGRAD_HIP=1, off by default) sends the 3x3 weight gradients of `_Conv2dK3` and
+    train_decoder._Conv2dK3Cat to ss_conv2d_k3_wgrad_fwd instead of the 3x3x3 kernel on depth-1 volumes: CUDA fp32 contiguous maps
+    inside the kernel's limits, and not where the exact-fp32 weight gradient was asked for (train_layers.WGRAD_ENGINE = "f32")."""
+    from . import train_layers as TL
+    ts = (g, x) if rem is None else (g, x, rem)
+    if not (_M().CONV2D_WGRAD_HIP and TL.WGRAD_ENGINE != "f32"):
+        return False
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()
+               and t.numel() > 0 and t.shape[0] == g.shape[0] and tuple(t.shape[2:]) == tuple(g.shape[2:]) for t in ts):
+        return False
+    B, _, H, W = g.shape
+    C0, C1, Cout = x.shape[1], 0 if rem is None else rem.shape[1], g.shape[1]
+    return (max(C0, C1, Cout) * H * W * 4 < 1 << 31 and B * H <= 0x7fffffff
+            and ((C0 + 31) // 32 + (C1 + 31) // 32) * ((Cout + 31) // 32) <= 65535)
+
+
+def conv2d_k3_wgrad_workspace_bytes(B, C0, C1, H, W, Cout):
+    import ctypes
+    n = ctypes.c_longlong(0)
+    status = _lib.load().ss_conv2d_k3_wgrad_workspace_bytes(B, C0, C1, H, W, Cout, ctypes.byref(n))
+    if status != 0:
+        raise _lib.SemStereoHipError(f"ss_conv2d_k3_wgrad_workspace_bytes failed ({status})")
+    return n.value
+
+
+def conv2d_k3_wgrad_hip(g, x, rem=None):
+    """grad_w [Cout, C0 (+ C1), 3, 3] of Conv2d(3x3, s1, p1, no bias) on x [B,C0,H,W] or on cat((x, rem), 1) (rem [B,C1,H,W], the
+    concatenation never formed) from g [B,Cout,H,W] (csrc/conv2d_wgrad.hip): no atomics, the same inputs give the same bits."""
+    g, x = _c(g), _c(x)
+    rem = None if rem is None else _c(rem)
+    dev = _lib.require_device(g, x, rem)
+    B, Cout, H, W = g.shape
+    C0, C1 = x.shape[1], 0 if rem is None else rem.shape[1]
+    assert tuple(x.shape) == (B, C0, H, W) and (rem is None or tuple(rem.shape) == (B, C1, H, W))
+    gw = torch.empty((Cout, C0 + C1, 3, 3), dtype=torch.float32, device=g.device)
+    work = torch.empty(conv2d_k3_wgrad_workspace_bytes(B, C0, C1, H, W, Cout) // 4, dtype=torch.float32, device=g.device)
+    with torch.cuda.device(dev):
+        call("ss_conv2d_k3_wgrad_fwd", ptr(g), ptr(x), ptr(rem), ptr(gw), ptr(work), B, C0, C1, H, W, Cout)
+    _count("wgrad2d")
+    return gw
+
+
 class _Conv2dK3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w):
@@ -245,7 +289,9 @@ class _Conv2dK3(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             wt = w.detach().transpose(0, 1).flip(2, 3).contiguous()
             gx = M.conv2d_bf16s_hip(g, M.pack_conv2d_weight_bf16s(wt, nt), w.shape[1], None, None, False, nt)
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and conv2d_k3_wgrad_applies(g, x):
+            gw = conv2d_k3_wgrad_hip(g, x)
+        elif ctx.needs_input_grad[1]:
             # depth-1 volumes through the 3x3x3 weight-gradient kernel: its kd = 1 plane is the 3x3 gradient
             gw = M.conv3d_wgrad_hip(g.unsqueeze(2), x.unsqueeze(2), w.shape[0], w.shape[1], 1)[:, :, 1].contiguous()
         return gx, gw

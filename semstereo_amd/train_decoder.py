@@ -11,7 +11,8 @@ ss_conv2d_k4s2_f16s_fwd (a 4x4 stride-2 convolution of the output's gradient wit
 ss_deconv2d_k4s2_wgrad_fwd (csrc/deconv2d_train.hip), bias gradient ss_channel_sum_fwd.  Each of the two gradients has its own seam
 (`DGRAD_HIP` / `WGRAD_HIP`) with aten.convolution_backward behind it.  `_Conv2dK3Cat`: forward ss_conv2d_bf16s_cat_fwd; data gradient
 by train._Conv2dK3's recipe -- the plain 3x3 kernel on the flipped, channel-swapped weight, once per half so that each source's
-gradient is written contiguously --; weight gradient from conv3d_wgrad_hip on depth-1 volumes, once per source.
+gradient is written contiguously --; weight gradient from conv3d_wgrad_hip on depth-1 volumes, once per source, or, with
+`engine.CONV2D_WGRAD_HIP` (SS_CONV2D_WGRAD_HIP=1, off by default), from one call of train.conv2d_k3_wgrad_hip on both sources.
 
 Opt-in: `engine.DECODER_TRAIN_HIP` (SS_DECODER_TRAIN_HIP=1), with `engine.TRAIN_HIP`, the decoder's own switch and the f16x3 engine.
 What the kernels are not built for -- a skip map of another size (the F.interpolate branch), CPU, float64, non-contiguous inputs, a
@@ -169,7 +170,9 @@ class _Conv2dK3Cat(torch.autograd.Function):
                 gy = E.conv2d_bf16s_hip(g, E.pack_conv2d_weight_bf16s(wt[:Cs].contiguous(), nt), Cs, None, None, False, nt)
             if ctx.needs_input_grad[1]:
                 grem = E.conv2d_bf16s_hip(g, E.pack_conv2d_weight_bf16s(wt[Cs:].contiguous(), nt), w.shape[1] - Cs, None, None, False, nt)
-        if ctx.needs_input_grad[2]:
+        if ctx.needs_input_grad[2] and T.conv2d_k3_wgrad_applies(g, y, rem):
+            gw = T.conv2d_k3_wgrad_hip(g, y, rem)           # (engine.CONV2D_WGRAD_HIP: one call, both sources, no cat and no slice copy)
+        elif ctx.needs_input_grad[2]:
             # depth-1 volumes through the 3x3x3 weight-gradient kernel (its kd = 1 plane is the 3x3 gradient), once per source
             g5 = g.unsqueeze(2)
             gw = torch.cat((M.conv3d_wgrad_hip(g5, y.unsqueeze(2), Cout, Cs, 1)[:, :, 1],
