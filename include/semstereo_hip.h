@@ -738,6 +738,37 @@ int ss_disparity_metrics_fwd(const float* est0, const float* est1, const float* 
 int ss_seg_confusion_fwd(const float* logits, const void* labels, int label_dtype, int B, int num_classes, int H, int W,
                          long long label_row_stride, long long label_image_stride, long long* joint, int accumulate, void* workspace,
                          long long workspace_bytes, ss_stream_t stream);
+/* ---- the evaluation step's image outputs (main_us3d.py:252, :265-268; main_whu.py:242, :250-251), csrc/vis.hip ----
+ * Streaming passes without atomics: a lane takes 4 consecutive pixels of a row (16-byte accesses where the address allows), results are
+ * planar [B,3,H,W], element offsets are 64-bit, every division is the IEEE one.  Nothing comes back to the host.  A map of 2^31 or more
+ * 4-pixel groups: -2.  ss_vis_workspace_bytes(kind) bytes of scratch, kind 0 = ss_image_minmax_fwd (the other calls need none). */
+int ss_vis_workspace_bytes(int kind, long long* bytes);
+/* disp_error_image_func.forward (utils/visualization.py:30-55) without its host copies and its twenty boolean-mask passes: est, gt
+ * [B,H,W] fp32 -> out [B,3,H,W] fp32.  e = min(|gt - est| / abs_thres, (|gt - est| / gt) / rel_thres) in fp32 (a NaN in either term
+ * gives NaN, as np.minimum); the pixel takes colour i of `table` where table[i][0] <= e < table[i][1], and black where gt is not valid
+ * or no row matches (NaN, +inf).  table: HOST memory, 10 rows of {lo, hi, r, g, b} floats -- gen_error_colormap() (:11-24) cast to
+ * float32 -- read during the call and passed to the kernel by value.  legend != 0: rows < 10, columns 20 i .. 20 i + 19 take colour i
+ * (:51-53), clipped to H and W, also where gt is not valid.  Valid: gt > 0 (:36); with is_signed != 0: lo <= gt < hi and gt != 0, the
+ * relative term over |gt| -- the signed disparities of US3D, where the reference's rule paints every negative ground truth black. */
+int ss_disp_error_image_fwd(const float* est, const float* gt, const float* table, int B, int H, int W, float abs_thres, float rel_thres,
+                            int legend, int is_signed, float lo, float hi, float* out, ss_stream_t stream);
+/* feature_vis (utils/mask_vis.py:5-31) without its host copy, and the same picture straight from a label map, for which the scripts
+ * build F.one_hot(label, 6).permute().float() only to take its argmax (main_us3d.py:266).  src_dtype -1: src = logits [B,C,H,W] fp32,
+ * C = num_classes <= 6 (more: -2); the class is the first maximum over the channels, a NaN counting as the maximum (np.argmax, as in
+ * ss_seg_confusion_fwd).  src_dtype 0 = int64, 1 = uint8, 2 = float32 (truncated toward zero): src = labels, pixel (b, h, x) at
+ * b * label_image_stride + h * label_row_stride + x elements (the strides are ignored for logits).  out [B,3,H,W], out_dtype 0 = float32,
+ * 1 = uint8, holds the palette of :10-15 with the values 0 and 255; a label outside [0, 6) gives black (the reference raises). */
+int ss_class_color_fwd(const void* src, int src_dtype, int B, int num_classes, int H, int W, long long label_row_stride,
+                       long long label_image_stride, void* out, int out_dtype, ss_stream_t stream);
+/* The per-image range that save_images (utils/experiment.py:84-99) asks of make_grid(normalize=True, scale_each=True):
+ * minmax[b] = {min, max} over the elements_per_image floats of image b.  Wave, LDS, one partial per workgroup in `workspace`, then a
+ * second small launch that reads the partials in a fixed order: the same bits on every call.  More than 1024 images: -2. */
+int ss_image_minmax_fwd(const float* x, int B, long long elements_per_image, float* minmax, void* workspace, long long workspace_bytes,
+                        ss_stream_t stream);
+/* ... and the normalisation itself: out = (clamp(x, lo, hi) - lo) / max(hi - lo, 1e-5f) in fp32 with {lo, hi} = minmax[b], x [B,C,P]
+ * with P = pixels_per_channel.  out is [B,C,P], or [B,3,P] with three equal channels for C = 1 (make_grid's single-channel rule).
+ * More than 65535 images: -2. */
+int ss_image_normalize_fwd(const float* x, const float* minmax, float* out, int B, int C, long long pixels_per_channel, ss_stream_t stream);
 /* Measurement aid (bench.py): a plain device copy, 16 bytes per lane, nontemporal -- the HBM rate a streaming kernel can
  * reach on this box, which SURVEY.md section 8(d) asks the bandwidth fractions to be read against.  bytes % 16 == 0. */
 int ss_tool_copy_fwd(const void* src, void* dst, long long bytes, ss_stream_t stream);

@@ -127,6 +127,11 @@ _SIGNATURES = {
     "ss_metrics_workspace_bytes": [_I, _P],
     "ss_disparity_metrics_fwd": [_P] * 7 + [_I, _I, ctypes.c_longlong] + [ctypes.c_float] * 6 + [_I, _P, _P, _P, _P, ctypes.c_longlong, _P],
     "ss_seg_confusion_fwd": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_longlong, ctypes.c_longlong, _P, _I, _P, ctypes.c_longlong, _P],
+    "ss_vis_workspace_bytes": [_I, _P],
+    "ss_disp_error_image_fwd": [_P, _P, _P, _I, _I, _I, ctypes.c_float, ctypes.c_float, _I, _I, ctypes.c_float, ctypes.c_float, _P, _P],
+    "ss_class_color_fwd": [_P, _I, _I, _I, _I, _I, ctypes.c_longlong, ctypes.c_longlong, _P, _I, _P],
+    "ss_image_minmax_fwd": [_P, _I, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P],
+    "ss_image_normalize_fwd": [_P, _P, _P, _I, _I, ctypes.c_longlong, _P],
 }
 EXPORTS = sorted(list(_SIGNATURES) + ["ss_abi_version", "ss_status_string", "ss_last_hip_error", "ss_ssr_param_count", "ss_reload_tuning",
                                            "ss_set_fill_hint", "ss_get_fill_hint", "ss_seghead_tail_workspace_bytes", "ss_deconv2d_k4s2_wgrad_workspace_bytes",

@@ -66,6 +66,18 @@ def install_metrics(script_module):
     return previous
 
 
+def install_visualization(script_module):
+    """The image outputs' counterpart of `install_metrics`: the scripts get disp_error_image_func and feature_vis by
+    `from utils import *` (main_us3d.py:16; utils/__init__.py:2, :6) and call them by bare name in test_sample (main_us3d.py:266-268),
+    so the drop-in is the same rebinding in the SCRIPT's module.  Returns {name: previous object} for `uninstall`."""
+    from . import visualization
+    previous = {}
+    for name in visualization.NAMES:
+        previous[name] = getattr(script_module, name, None)
+        setattr(script_module, name, getattr(visualization, name))
+    return previous
+
+
 def uninstall(model_module, previous):
     for name, obj in previous.items():
         if obj is None:
