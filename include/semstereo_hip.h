@@ -769,6 +769,37 @@ int ss_image_minmax_fwd(const float* x, int B, long long elements_per_image, flo
  * with P = pixels_per_channel.  out is [B,C,P], or [B,3,P] with three equal channels for C = 1 (make_grid's single-channel rule).
  * More than 65535 images: -2. */
 int ss_image_normalize_fwd(const float* x, const float* minmax, float* out, int B, int C, long long pixels_per_channel, ss_stream_t stream);
+/* ---- sample preparation (datasets/us3d_.py:70-215, datasets/whu_dataset.py:42-92, datasets/data_io.py:6-13), csrc/sample_prep.hip ----
+ * What the reference's __getitem__ computes on the host for every item, from the raw arrays on the device.  Streaming passes: a lane
+ * takes 4 consecutive pixels of a row, wide accesses where the address allows.  No atomics.  Nothing comes back to the host.  A tensor
+ * of 2^31 or more elements: -2.
+ * ss_prep_workspace_bytes: scratch of the luma / gradient pair for a [B,H,W] batch -- integer partial sums, then the uint8 luma plane. */
+int ss_prep_workspace_bytes(int B, int H, int W, long long* bytes);
+/* ToTensor + Normalize of both views: left, right uint8 [B,H,W,3] -> out_left, out_right float32 [B,3,H,W], out[b][c][y][x] =
+ * table[c][u].  table: DEVICE memory, float [3][256], (u / 255 - mean[c]) / std[c] built by the caller in fp32 with the constants of
+ * data_io.py:7-8 -- no division runs here.  right and out_right may both be NULL (one view). */
+int ss_prep_views_fwd(const unsigned char* left, const unsigned char* right, const float* table, int B, int H, int W, float* out_left,
+                      float* out_right, ss_stream_t stream);
+/* cv2.resize(a, (w // k, h // k), INTER_NEAREST) for every requested level in one launch, H and W divisible by 16 (other sizes: -2): the
+ * source pixel of (y, x) is (y k, x k).  disparity [B,H,W] contiguous, disp_dtype 0 = float32, 1 = int32; every disparity output is
+ * float(v) * disp_scale in fp32 (WHU: 1 / 256, exact).  label: label_dtype 0 = int64, 1 = uint8, 2 = float32, pixel (b, h, x) at
+ * b * label_image_stride + h * label_row_stride + x elements; every label output is the value widened to float32.  Outputs:
+ * disparity_out, label_out [B,H,W]; disparity_k, label_k [B,H/k,W/k].  A NULL output is skipped; a source is read only where sampled
+ * and may be NULL if none of its outputs is asked for. */
+int ss_prep_pyramid_fwd(const void* disparity, int disp_dtype, float disp_scale, const void* label, int label_dtype,
+                        long long label_row_stride, long long label_image_stride, int B, int H, int W, float* disparity_out,
+                        float* disparity_4, float* disparity_8, float* disparity_16, float* label_out, float* label_2, float* label_4,
+                        ss_stream_t stream);
+/* PIL's convert("L") of left uint8 [B,H,W,3], L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16, written as a uint8 plane into
+ * `workspace` together with the parts of S1 = sum L and S2 = sum L^2 per image as 64-bit integers (wave, LDS, one partial pair per
+ * workgroup; the gradient pass adds them: integer sums, exact in any order, so two calls give the same bits).  H W > 2^23 (where
+ * N S2 - S1^2 leaves 64 bits) or more than 65535 images: -2. */
+int ss_prep_luma_stats_fwd(const unsigned char* left, int B, int H, int W, void* workspace, long long workspace_bytes, ss_stream_t stream);
+/* gx, gy float32 [B,1,H,W] of the dataset (us3d_.py:98-109) from the workspace that ss_prep_luma_stats_fwd filled on the same stream:
+ * mean = S1 / N, std = sqrt(N S2 - S1^2) / N, z[L] = (L - mean) / std in double (a 256-entry table per image in LDS),
+ * gx = float(z(y, x-1) - z(y, x+1)), gy = float(z(y-1, x) - z(y+1, x)), zero outside the image (convolve2d flips the kernel).  The
+ * centre tap 0 * z(y, x) is kept: a constant image (std = 0) is NaN on every pixel, as in the reference. */
+int ss_prep_gradients_fwd(const void* workspace, long long workspace_bytes, int B, int H, int W, float* gx, float* gy, ss_stream_t stream);
 /* Measurement aid (bench.py): a plain device copy, 16 bytes per lane, nontemporal -- the HBM rate a streaming kernel can
  * reach on this box, which SURVEY.md section 8(d) asks the bandwidth fractions to be read against.  bytes % 16 == 0. */
 int ss_tool_copy_fwd(const void* src, void* dst, long long bytes, ss_stream_t stream);

@@ -8,16 +8,19 @@
   metrics   the evaluation step's metrics under the reference's names (utils/metrics.py), install_metrics(script_module)
   visualization  the evaluation step's image outputs under the reference's names (utils/visualization.py, utils/mask_vis.py),
             install_visualization(script_module)
+  data      the datasets' sample preparation on the device (datasets/us3d_.py, datasets/whu_dataset.py): normalised views, ground-truth
+            pyramids, gx / gy; RawStereoDataset and DeviceLoader
   dist      one-process-per-GPU batch sharding (RCCL / gloo)
 
 The compute lives in csrc/libsemstereo_hip.so behind the C ABI of include/semstereo_hip.h.
 Nothing here falls back to the CPU or to the test oracle.
 """
-from . import _lib, dist, engine, losses, metrics, modules, ops, ops_unsigned, segment, train_layers, visualization  # noqa: F401
+from . import _lib, data, dist, engine, losses, metrics, modules, ops, ops_unsigned, segment, train_layers, visualization  # noqa: F401
 from .install import accelerate, install, install_losses, install_metrics, install_visualization, restore_forward, uninstall  # noqa: F401
 from .losses import LRSC_loss, model_label_loss, model_loss_test, model_loss_train, train_objective  # noqa: F401
 from .metrics import EvalAverager, SegmentationMetric, disparity_metrics, eval_metrics  # noqa: F401
 from .visualization import disp_error_image_func, eval_images, feature_vis, label_vis, normalize_image  # noqa: F401
+from .data import DeviceLoader, RawStereoDataset, image_gradients, nearest_pyramid, normalize_views, prepare_sample  # noqa: F401
 from .segment import GraphedSegment, HotSegment, PairPipeline  # noqa: F401
 
 __version__ = "0.1.0"

@@ -132,10 +132,14 @@ _SIGNATURES = {
     "ss_class_color_fwd": [_P, _I, _I, _I, _I, _I, ctypes.c_longlong, ctypes.c_longlong, _P, _I, _P],
     "ss_image_minmax_fwd": [_P, _I, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P],
     "ss_image_normalize_fwd": [_P, _P, _P, _I, _I, ctypes.c_longlong, _P],
+    "ss_prep_views_fwd": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "ss_prep_pyramid_fwd": [_P, _I, ctypes.c_float, _P, _I, ctypes.c_longlong, ctypes.c_longlong, _I, _I, _I] + [_P] * 7 + [_P],
+    "ss_prep_luma_stats_fwd": [_P, _I, _I, _I, _P, ctypes.c_longlong, _P],
+    "ss_prep_gradients_fwd": [_P, ctypes.c_longlong, _I, _I, _I, _P, _P, _P],
 }
 EXPORTS = sorted(list(_SIGNATURES) + ["ss_abi_version", "ss_status_string", "ss_last_hip_error", "ss_ssr_param_count", "ss_reload_tuning",
                                            "ss_set_fill_hint", "ss_get_fill_hint", "ss_seghead_tail_workspace_bytes", "ss_deconv2d_k4s2_wgrad_workspace_bytes",
-                                           "ss_conv2d_k3_wgrad_workspace_bytes"])
+                                           "ss_conv2d_k3_wgrad_workspace_bytes", "ss_prep_workspace_bytes"])
 
 _lib = None
 
@@ -170,6 +174,8 @@ def load():
     lib.ss_deconv2d_k4s2_wgrad_workspace_bytes.argtypes = [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]
     lib.ss_conv2d_k3_wgrad_workspace_bytes.restype = _I
     lib.ss_conv2d_k3_wgrad_workspace_bytes.argtypes = [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]
+    lib.ss_prep_workspace_bytes.restype = _I
+    lib.ss_prep_workspace_bytes.argtypes = [_I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]
     if lib.ss_abi_version() != ABI_VERSION:
         raise SemStereoHipError(f"ABI mismatch: library {lib.ss_abi_version()} != binding {ABI_VERSION}; rebuild")
     for name, argtypes in _SIGNATURES.items():
