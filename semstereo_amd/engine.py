@@ -761,7 +761,14 @@ DECODER_TRAIN_HIP = os.environ.get("SS_DECODER_TRAIN_HIP", "0") != "0"
 #: from ss_conv2d_k3_wgrad_fwd (csrc/conv2d_wgrad.hip: one call for both sources, no atomics) instead of the 3x3x3 kernel on depth-1
 #: volumes; off by default: it changes the bits of those gradients.  Read at each call.
 CONV2D_WGRAD_HIP = os.environ.get("SS_CONV2D_WGRAD_HIP", "0") != "0"
-LOSS_HIP = os.environ.get("SS_LOSS_HIP", "1") != "0"      # 0: semstereo_amd.losses keeps its PyTorch composition (no boolean indexing) on the GPU too
+def _fuse_training_on():
+    """SS_FUSE_TRAINING=0: a model routed by `accelerate(model, fuse_training=True)` hands its train() / autograd calls back to its own
+    forward(), as without the argument (install.fused_training_forward).  Read from the environment at each call, so a launcher can
+    turn the route off without touching the script."""
+    return os.environ.get("SS_FUSE_TRAINING", "1") != "0"
+
+
+LOSS_HIP = os.environ.get("SS_LOSS_HIP", "1") != "0"    # 0: semstereo_amd.losses keeps its PyTorch composition (no boolean indexing) on the GPU too
 METRICS_HIP = os.environ.get("SS_METRICS_HIP", "1") != "0"      # 0: semstereo_amd.metrics keeps its PyTorch composition (no boolean indexing, no .cpu()) on the GPU too
 VIS_HIP = os.environ.get("SS_VIS_HIP", "1") != "0"      # 0: semstereo_amd.visualization keeps its PyTorch composition (no boolean indexing, no .cpu()) on the GPU too
 DATA_HIP = os.environ.get("SS_DATA_HIP", "1") != "0"      # 0: semstereo_amd.data keeps its PyTorch composition (no boolean indexing, no .item()) on the GPU too

@@ -184,10 +184,13 @@ class HotSegment(nn.Module):
         cost_att = self.classif_att_(self.hourglass_att(cost_att))                             # :277-278
         if rel is not None:
             rel("cls")
-        if (not fast and getattr(self, "FUSED", HotSegment.FUSED) and not M._inference(self, fl4, fr4, fl8, fr8)
+        training = not fast and not M._inference(self, fl4, fr4, fl8, fr8)
+        if (training and getattr(self, "FUSED", HotSegment.FUSED)
                 and isinstance(cost_att, torch.Tensor) and T.attention_tail_applies(cost_att, r4, H4, W4, fl4, fr4, TOPK)):
             # training / autograd (main_us3d.py:186-222): :279-310 as the three fused launches with their backward kernels (train.py)
             return T.attention_tail(cost_att, fl4, fr4, self.gamma, self.beta, r4, H4, W4, TOPK)
+        if training:                    # (the fused tail declined: the statements below run under autograd, and are counted)
+            M.PATH_COUNTS["train_tail_statements"] = M.PATH_COUNTS.get("train_tail_statements", 0) + 1
         if fast and ops.upsample_softmax_regression_applies(cost_att, m4, H4, W4, r4):
             att_weights, pred0, var = ops.upsample_softmax_regression(cost_att, m4, H4, W4, _range=r4)    # :279-285 fused
         elif fast:
@@ -303,6 +306,8 @@ class HotSegment(nn.Module):
                 # training (r06): :316-318 as one launch each way instead of a warp, a cat and a multiply and their three backwards
                 volume = T.concat_volume_sampled(cl, cr, samples, att_topk, margin=max(self.maxdisp // 4, 1))
             else:
+                if torch.is_grad_enabled():     # (the one-launch form declined, e.g. W/4 no multiple of 64: counted)
+                    M.PATH_COUNTS["train_concat_statements"] = M.PATH_COUNTS.get("train_concat_statements", 0) + 1
                 right_w, left_b = ops.SpatialTransformer_grid(cl, cr, samples)                 # :241-242 (concat_volume_generator)
                 volume = torch.cat((left_b, right_w), dim=1)                                   # :243
                 volume = att_topk * volume                                                     # :318
