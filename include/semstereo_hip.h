@@ -17,6 +17,7 @@
  *  - `stream` is a hipStream_t (NULL = the null stream); launches are asynchronous;
  *  - re-entrant, no global mutable state, current device of the calling thread;
  *  - return value: SS_OK (0) or a negative ss_status; nothing throws across the ABI.
+ *  - parameters are int, long long, float, double, ss_stream_t or pointers: semstereo_amd/_lib.py binds from these declarations and refuses any other type.
  */
 #ifndef SEMSTEREO_HIP_H
 #define SEMSTEREO_HIP_H

@@ -2,154 +2,65 @@
 
 There is deliberately NO fallback: if the shared library is missing or a kernel
 returns an error, the caller gets an exception.  PyTorch is used only for
-device memory and streams; the signatures below carry raw pointers and sizes.
+device memory and streams; the signatures carry raw pointers and sizes.
+
+The header is the one definition of the boundary: load() reads every declaration of it and binds it.  A parameter is an int,
+a long long, a float, a double, an ss_stream_t or (anything with a `*`) a pointer; any other type is an error, never a guess.
 """
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  (must be imported first: it loads the HIP runtime the library binds to)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsemstereo_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "semstereo_hip.h")
 ABI_VERSION = 20
 
-_P = ctypes.c_void_p
-_I = ctypes.c_int
+_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "double": ctypes.c_double,
+            "ss_stream_t": ctypes.c_void_p}
+_RETURNS = {"int": ctypes.c_int, "const char*": ctypes.c_char_p}
+_DECLARATION = re.compile(r"([\w \t*]+?)\s*\b(ss_\w+)\s*\(([^()]*)\)\s*;")
 
-# name -> argument types (return type is always int status); mirrors include/semstereo_hip.h
-_SIGNATURES = {
-    "ss_groupwise_correlation_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ss_gwc_volume_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_gwc_patch_gate_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_gwc_volume_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_concat_volume_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_concat_volume_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_warp_sampled_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_warp_sampled_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_concat_sampled_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_concat_sampled_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ss_concat_sampled_presplit_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_conv3d_presplit_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_stem_left_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_stem_left_fused_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_stem_left_mfma_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ss_pack_stem_left_weights_f16s": [_P, _P, _I, _I, _P],
-    "ss_warp_correlation_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_disparity_regression_fwd": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_disparity_regression_bwd": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_disparity_variance_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_softmax_regression_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_upsample_softmax_regression_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_regression_topk_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_regression_topk_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_sample_strength_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "ss_topk_candidates_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ss_channel_gate_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_channel_att_logits_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_ssr_upsample_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "ss_ssr_upsample_train_fwd": [_P, _P, _P, _P, _P, _P] + [_P] * 12 + [ctypes.c_float] * 4 + [ctypes.c_double] * 4
-                                 + [_I, _I, _I, _I, _I, _P, ctypes.c_longlong, _P],
-    "ss_ssr_upsample_train_bwd": [_P] * 10 + [_I, _I, _I, _I, _I, _P, ctypes.c_longlong, _P],
-    "ss_conv3d_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_conv3d_bf16s_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_conv3d_bf16s_partial_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_conv3d_gather_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_pack_conv3d_weights_bf16s": [_P, _P, _I, _I, _P],
-    "ss_pack_conv3d_weights_f16s": [_P, _P, _I, _I, _P],
-    "ss_conv2d_bf16s_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_conv2d_bf16s_pair_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_pack_conv2d_weights_bf16s": [_P, _P, _I, _I, _P],
-    "ss_conv2d_bf16s_cat_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_deconv2d_bf16s_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_deconv2d_bf16s_pair_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_pack_deconv2d_weights_f16s": [_P, _P, _I, _I, _P],
-    "ss_pack_conv2d_weights_f16s": [_P, _P, _I, _I, _P],
-    "ss_conv2d_k4s2_f16s_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_pack_conv2d_k4s2_weights_f16s": [_P, _P, _I, _I, _P],
-    "ss_deconv2d_k4s2_wgrad_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_conv2d_k3_wgrad_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ss_conv2d_k1_f16s_fwd": [_P, _P, _P, _P, _P, _I, _I, ctypes.c_longlong, _I, _I, _P],
-    "ss_conv2d_k1_f16s_pair_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_longlong, _I, _I, _P],
-    "ss_pack_conv2d_k1_weights_f16s": [_P, _P, _I, _I, _P],
-    "ss_seghead_logits_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_pack_seghead_weights_f16s": [_P, _P, _I, _P],
-    "ss_bilinear_up2_fwd": [_P, _P, _I, _I, _I, _I, _P],
-    "ss_seghead_tail_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ss_seghead_tail_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ss_conv3d_head_bf16s_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_conv3d_head_bf16s_cl_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_conv3d_bf16s_cl_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_pack_classifier_head_weights": [_P, _P, _P],
-    "ss_conv3d_classifier_fused_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ss_regression_topk_patched_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_pack_conv3d_head_weights_bf16s": [_P, _P, _I, _P],
-    "ss_pack_conv3d_head_weights_f16s": [_P, _P, _I, _P],
-    "ss_conv3d_pointwise_bf16s_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_longlong, _I, _I, _P],
-    "ss_pack_pointwise_weights_bf16s": [_P, _P, _I, _I, _P],
-    "ss_deconv3d_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_pack_deconv3d_weights_f16s": [_P, _P, _I, _I, _P],
-    "ss_deconv3d_bf16s_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_pack_deconv3d_weights_bf16s": [_P, _P, _I, _I, _I, _P],
-    "ss_pack_conv3d_weights": [_P, _P, _I, _I, _I, _I, _P],
-    "ss_conv3d_wgrad_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_conv3d_wgrad_bf16s_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_depthwise_patch_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_window_attention_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_window_attention_core_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_tool_copy_fwd": [_P, _P, ctypes.c_longlong, _P],
-    "ss_upsample_softmax_regression_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_sample_strength_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "ss_sample_strength_bwd_ws": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "ss_topk_candidates_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "ss_batchnorm_train_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_longlong, ctypes.c_float, _I, _P],
-    "ss_batchnorm_train_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_longlong, _I, _P],
-    "ss_batchnorm_train_res_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_longlong, ctypes.c_float, _I, _P],
-    "ss_batchnorm_train_res_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_longlong, _I, _P],
-    "ss_group_normalise_fwd": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_float, _P],
-    "ss_group_normalise_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.c_float, _P],
-    "ss_batchnorm_train_fwd_rs": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_double, _I, _I, ctypes.c_longlong, ctypes.c_float, _I, _P],
-    "ss_batchnorm_bwd_pg": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_longlong, _I, _P],
-    "ss_batchnorm_eval_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_longlong, _I, _P],
-    "ss_batchnorm_eval_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_longlong, _I, _P],
-    "ss_channel_sum_fwd": [_P, _P, _I, _I, ctypes.c_longlong, _P],
-    "ss_conv_k1_wgrad_fwd": [_P, _P, _P, _I, _I, _I, ctypes.c_longlong, _P],
-    "ss_depthwise_patch_wgrad_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_channel_gate_bwd_logits": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "ss_window_attention_core_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_window_attention_core_pad_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "ss_loss_workspace_bytes": [_I, _P],
-    "ss_disparity_loss_fwd": [_P, _P, _P, ctypes.c_longlong] * 4 + [ctypes.c_float] * 6 + [_I, _I, _P, _P, _P, ctypes.c_longlong, _P],
-    "ss_disparity_loss_bwd": [_P, _P, _P, _P, ctypes.c_longlong] * 4 + [ctypes.c_float] * 6 + [_I, _I, _P, _P, _P],
-    "ss_label_loss_fwd": [_P, _P, _I, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, ctypes.c_longlong, _P],
-    "ss_label_loss_bwd": [_P, _P, _I, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P],
-    "ss_lrsc_loss_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_longlong, _P],
-    "ss_lrsc_loss_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "ss_metrics_workspace_bytes": [_I, _P],
-    "ss_disparity_metrics_fwd": [_P] * 7 + [_I, _I, ctypes.c_longlong] + [ctypes.c_float] * 6 + [_I, _P, _P, _P, _P, ctypes.c_longlong, _P],
-    "ss_seg_confusion_fwd": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_longlong, ctypes.c_longlong, _P, _I, _P, ctypes.c_longlong, _P],
-    "ss_vis_workspace_bytes": [_I, _P],
-    "ss_disp_error_image_fwd": [_P, _P, _P, _I, _I, _I, ctypes.c_float, ctypes.c_float, _I, _I, ctypes.c_float, ctypes.c_float, _P, _P],
-    "ss_class_color_fwd": [_P, _I, _I, _I, _I, _I, ctypes.c_longlong, ctypes.c_longlong, _P, _I, _P],
-    "ss_image_minmax_fwd": [_P, _I, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P],
-    "ss_image_normalize_fwd": [_P, _P, _P, _I, _I, ctypes.c_longlong, _P],
-    "ss_prep_views_fwd": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
-    "ss_prep_pyramid_fwd": [_P, _I, ctypes.c_float, _P, _I, ctypes.c_longlong, ctypes.c_longlong, _I, _I, _I] + [_P] * 7 + [_P],
-    "ss_prep_luma_stats_fwd": [_P, _I, _I, _I, _P, ctypes.c_longlong, _P],
-    "ss_prep_gradients_fwd": [_P, ctypes.c_longlong, _I, _I, _I, _P, _P, _P],
-}
-EXPORTS = sorted(list(_SIGNATURES) + ["ss_abi_version", "ss_status_string", "ss_last_hip_error", "ss_ssr_param_count", "ss_reload_tuning",
-                                           "ss_set_fill_hint", "ss_get_fill_hint", "ss_seghead_tail_workspace_bytes", "ss_deconv2d_k4s2_wgrad_workspace_bytes",
-                                           "ss_conv2d_k3_wgrad_workspace_bytes", "ss_prep_workspace_bytes"])
-
+_SIGNATURES = {}      # name -> argument types of every declared function (filled by load())
+EXPORTS = []          # every declared name, sorted (filled by load())
 _lib = None
+_BYTES = {}           # (query, args) -> bytes: the workspace queries are pure functions of their arguments
 
 
 class SemStereoHipError(RuntimeError):
     pass
 
 
+def _ctype(param, decl):
+    if "*" in param:
+        return ctypes.c_void_p
+    words = [w for w in param.split() if w != "const"]
+    for kind in (" ".join(words), " ".join(words[:-1])):       # without and with a parameter name
+        if kind in _SCALARS:
+            return _SCALARS[kind]
+    raise SemStereoHipError(f"include/semstereo_hip.h: `{decl}`: parameter `{param}` is none of int, long long, float, double, "
+                            f"ss_stream_t or a pointer")
+
+
+def parse_header(text):
+    """C declarations `(int|const char*) ss_name(params);` -> {name: (restype, [argtypes])} in ctypes classes."""
+    out = {}
+    for m in _DECLARATION.finditer(re.sub(r"/\*.*?\*/", "", text, flags=re.S)):
+        decl = " ".join(m.group(0).split())
+        ret = re.sub(r"\s*\*", "*", " ".join(m.group(1).split()))
+        if ret not in _RETURNS:
+            raise SemStereoHipError(f"include/semstereo_hip.h: `{decl}`: return type `{ret}` is neither int nor const char*")
+        params = [p.strip() for p in m.group(3).split(",")]
+        if params in ([""], ["void"]):
+            params = []
+        out[m.group(2)] = (_RETURNS[ret], [_ctype(p, decl) for p in params])
+    return out
+
+
 def load():
-    """Load the shared library once; raise (never fall back) if that is impossible."""
+    """Load the shared library once and bind every declaration of the header; raise (never fall back) if that is impossible."""
     global _lib
     if _lib is not None:
         return _lib
@@ -158,30 +69,15 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"or `make -C semstereo_amd/csrc`. There is no CPU or PyTorch fallback for the HIP path.")
     lib = ctypes.CDLL(LIB_PATH)
-    lib.ss_abi_version.restype = _I
-    lib.ss_status_string.restype = ctypes.c_char_p
-    lib.ss_status_string.argtypes = [_I]
-    lib.ss_last_hip_error.restype = ctypes.c_char_p
-    lib.ss_reload_tuning.restype = _I
-    lib.ss_reload_tuning.argtypes = []
-    lib.ss_set_fill_hint.restype = _I          # (returns the previous value, not a status)
-    lib.ss_set_fill_hint.argtypes = [_I]
-    lib.ss_get_fill_hint.restype = _I
-    lib.ss_get_fill_hint.argtypes = []
-    lib.ss_seghead_tail_workspace_bytes.restype = _I   # (no stream argument: bound apart from _SIGNATURES)
-    lib.ss_seghead_tail_workspace_bytes.argtypes = [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]
-    lib.ss_deconv2d_k4s2_wgrad_workspace_bytes.restype = _I
-    lib.ss_deconv2d_k4s2_wgrad_workspace_bytes.argtypes = [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]
-    lib.ss_conv2d_k3_wgrad_workspace_bytes.restype = _I
-    lib.ss_conv2d_k3_wgrad_workspace_bytes.argtypes = [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]
-    lib.ss_prep_workspace_bytes.restype = _I
-    lib.ss_prep_workspace_bytes.argtypes = [_I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]
+    with open(HEADER_PATH) as f:
+        declared = parse_header(f.read())
+    for name, (restype, argtypes) in declared.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.ss_abi_version() != ABI_VERSION:
         raise SemStereoHipError(f"ABI mismatch: library {lib.ss_abi_version()} != binding {ABI_VERSION}; rebuild")
-    for name, argtypes in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = _I
-        fn.argtypes = argtypes
+    _SIGNATURES.update((name, argtypes) for name, (_, argtypes) in declared.items())
+    EXPORTS[:] = sorted(declared)
     _lib = lib
     return lib
 
@@ -204,6 +100,17 @@ def call(name, *args):
         if status == -3:
             msg += ": " + lib.ss_last_hip_error().decode()
         raise SemStereoHipError(f"{name} failed ({status}): {msg}")
+
+
+def query_bytes(name, *args):
+    """Bytes of scratch a `*_workspace_bytes` entry point asks for (no stream, no device: asked once per argument list)."""
+    if (name, args) not in _BYTES:
+        n = ctypes.c_longlong(0)
+        status = getattr(load(), name)(*args, ctypes.byref(n))
+        if status != 0:
+            raise SemStereoHipError(f"{name} failed ({status})")
+        _BYTES[(name, args)] = int(n.value)
+    return _BYTES[(name, args)]
 
 
 def require_device(*tensors):

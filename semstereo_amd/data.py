@@ -33,7 +33,6 @@ The arithmetic, defined once and used by both paths:
 Departures from the reference: every entry is a tensor on the inputs' device (the reference returns numpy arrays for `disparity`, the
 pyramid levels and `label`, which the collate turns into the same tensors); the statistics are the exact-integer form above.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -41,19 +40,16 @@ import torch
 
 from . import _lib
 from . import engine as E
+from ._host import LABEL_CODES, _const, _nograd, count
 from ._lib import call, ptr
-from .engine import PATH_COUNTS
 
 #: datasets/data_io.py:7-8
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 DISP_LEVELS, LABEL_LEVELS = (4, 8, 16), (2, 4)
 MAX_STAT_PIXELS = 2 ** 23                    # N S2 - S1^2 is exact in 64 bits up to here
-_LABEL_CODES = {torch.int64: 0, torch.uint8: 1, torch.float32: 2}       # include/semstereo_hip.h: label_dtype
 _DISP_CODES = {torch.float32: 0, torch.int32: 1}
 _MAX_ELEMENTS = 2 ** 31
-_CONST = {}
 _TABLE = []
-_WS_BYTES = {}
 
 #: the reference's keys per dataset kind and branch (us3d_.py:184-215, whu_dataset.py:68-92)
 KEYS = {
@@ -63,19 +59,6 @@ KEYS = {
     ("whu", False): ("left", "right", "disparity", "top_pad", "right_pad", "left_filename", "gx", "gy"),
 }
 _PASS_THROUGH = ("top_pad", "right_pad", "left_filename")
-
-
-def _count(hip, n=1):
-    key = "data_hip" if hip else "data_torch"
-    PATH_COUNTS[key] = PATH_COUNTS.get(key, 0) + n
-
-
-def _nograd(fn):
-    def wrapper(*args, **kwargs):
-        with torch.no_grad():
-            return fn(*args, **kwargs)
-    wrapper.__name__, wrapper.__doc__ = fn.__name__, fn.__doc__
-    return wrapper
 
 
 def view_table():
@@ -89,14 +72,6 @@ def view_table():
     return _TABLE[0]
 
 
-def _const(key, device, make):
-    """A small constant tensor on `device`, uploaded once (without waiting)."""
-    k = (key, str(device))
-    if k not in _CONST:
-        _CONST[k] = make().to(device, non_blocking=True)
-    return _CONST[k]
-
-
 def _hip(*tensors):
     """The kernels take these tensors: the switch is on and all of them are contiguous CUDA tensors on one device."""
     if not E.DATA_HIP:
@@ -107,13 +82,7 @@ def _hip(*tensors):
 
 def workspace_bytes(B, H, W):
     """Scratch of the luma / gradient pair (asked once per shape)."""
-    if (B, H, W) not in _WS_BYTES:
-        n = ctypes.c_longlong(0)
-        status = _lib.load().ss_prep_workspace_bytes(B, H, W, ctypes.byref(n))
-        if status != 0:
-            raise _lib.SemStereoHipError(f"ss_prep_workspace_bytes failed ({status})")
-        _WS_BYTES[(B, H, W)] = int(n.value)
-    return _WS_BYTES[(B, H, W)]
+    return _lib.query_bytes("ss_prep_workspace_bytes", B, H, W)
 
 
 # ------------------------------------------------------------------------------------------------ views
@@ -138,13 +107,13 @@ def normalize_views(left_u8, right_u8=None):
     assert all(_is_views(v) for v in views) and all(v.shape == left_u8.shape for v in views), "views are [B,H,W,3]"
     B, H, W, _ = left_u8.shape
     if all(v.dtype == torch.uint8 for v in views) and _hip(*views) and left_u8.numel() < _MAX_ELEMENTS:
-        _count(True)
+        count("data_hip")
         table = _const("view_table", left_u8.device, view_table)
         outs = [torch.empty((B, 3, H, W), dtype=torch.float32, device=left_u8.device) for _ in views]
         with torch.cuda.device(left_u8.device):
             call("ss_prep_views_fwd", ptr(left_u8), ptr(right_u8), ptr(table), B, H, W, ptr(outs[0]), ptr(outs[1]) if right_u8 is not None else None)
     else:
-        _count(False)
+        count("data_torch")
         outs = [_views_torch(v if v.dtype == torch.uint8 else v.clamp(0, 255).to(torch.uint8)) for v in views]
     return outs[0] if right_u8 is None else (outs[0], outs[1])
 
@@ -185,11 +154,11 @@ def nearest_pyramid(disparity, label=None, disp_levels=DISP_LEVELS, label_levels
     plain = disparity.dtype == torch.float32 and scale == 1.0                   # `disparity` passes through
     hip = (H % 16 == 0 and W % 16 == 0 and 0 < disparity.numel() < _MAX_ELEMENTS and set(disp_levels) <= set(DISP_LEVELS)
            and set(label_levels) <= set(LABEL_LEVELS) and disparity.dtype in _DISP_CODES and _hip(disparity)
-           and (label is None or (label.is_cuda and label.device == disparity.device and label.dtype in _LABEL_CODES))
+           and (label is None or (label.is_cuda and label.device == disparity.device and label.dtype in LABEL_CODES))
            and (label is not None or disp_levels or not plain))
     out = {}
     if hip:
-        _count(True)
+        count("data_hip")
         dev = disparity.device
         new = lambda k: torch.empty((B, H // k, W // k), dtype=torch.float32, device=dev)                  # noqa: E731
         out["disparity"] = disparity if plain else new(1)
@@ -200,7 +169,7 @@ def nearest_pyramid(disparity, label=None, disp_levels=DISP_LEVELS, label_levels
             y = label
             if y.stride(2) != 1 or y.stride(1) < W or (B > 1 and y.stride(0) < (H - 1) * y.stride(1) + W):
                 y = y.contiguous()
-            code, row = _LABEL_CODES[y.dtype], y.stride(1)
+            code, row = LABEL_CODES[y.dtype], y.stride(1)
             img = max(y.stride(0), (H - 1) * row + W)                            # (the stride of a batch of one is arbitrary)
             out["label"] = new(1)
             for k in label_levels:
@@ -210,7 +179,7 @@ def nearest_pyramid(disparity, label=None, disp_levels=DISP_LEVELS, label_levels
                  None if plain else ptr(out["disparity"]), ptr(out.get("disparity_4")), ptr(out.get("disparity_8")),
                  ptr(out.get("disparity_16")), ptr(out.get("label")), ptr(out.get("label_2")), ptr(out.get("label_4")))
     else:
-        _count(False)
+        count("data_torch")
         d = _scaled(disparity, scale)
         out["disparity"] = d
         for k in disp_levels:
@@ -267,7 +236,7 @@ def image_gradients(left_u8):
     assert _is_views(left_u8), "the view is [B,H,W,3]"
     B, H, W, _ = left_u8.shape
     if (left_u8.dtype == torch.uint8 and _hip(left_u8) and H * W <= MAX_STAT_PIXELS and B <= 65535 and left_u8.numel() < _MAX_ELEMENTS):
-        _count(True)
+        count("data_hip")
         dev = left_u8.device
         ws = torch.empty(workspace_bytes(B, H, W) // 8, dtype=torch.int64, device=dev)
         gx = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
@@ -276,7 +245,7 @@ def image_gradients(left_u8):
             call("ss_prep_luma_stats_fwd", ptr(left_u8), B, H, W, ptr(ws), ws.numel() * 8)
             call("ss_prep_gradients_fwd", ptr(ws), ws.numel() * 8, B, H, W, ptr(gx), ptr(gy))
         return gx, gy
-    _count(False)
+    count("data_torch")
     return _gradients_torch(left_u8 if left_u8.dtype == torch.uint8 else left_u8.clamp(0, 255).to(torch.uint8))
 
 

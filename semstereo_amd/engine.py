@@ -14,9 +14,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
+from ._host import PATH_COUNTS  # (the one dictionary: `engine.PATH_COUNTS` and `modules.PATH_COUNTS` are this object)
 from ._lib import call, ptr
-
-PATH_COUNTS = {"hip": 0, "torch": 0}
 
 
 def _inference(module, *tensors):

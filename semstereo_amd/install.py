@@ -32,6 +32,14 @@ from . import ops
 from . import segment
 
 
+def _rebind(module, names, source):
+    previous = {}
+    for name in names:
+        previous[name] = getattr(module, name, None)
+        setattr(module, name, getattr(source, name))
+    return previous
+
+
 def install(model_module, names=ops.REFERENCE_NAMES, unsigned=False):
     """setattr(model_module, name, hip_op) for every hot-path callable.  Rebinding
     `models.submodule.X` alone would not be enough: the star-import copied the binding.
@@ -39,12 +47,7 @@ def install(model_module, names=ops.REFERENCE_NAMES, unsigned=False):
     models/SemStereo_WHU.py needs in its globals to run at all (see ops_unsigned's docstring).
     Returns {name: previous object} so `uninstall` can restore it."""
     from . import ops_unsigned
-    lib = ops_unsigned if unsigned else ops
-    previous = {}
-    for name in names:
-        previous[name] = getattr(model_module, name, None)
-        setattr(model_module, name, getattr(lib, name))
-    return previous
+    return _rebind(model_module, names, ops_unsigned if unsigned else ops)
 
 
 def install_losses(script_module):
@@ -52,11 +55,7 @@ def install_losses(script_module):
     model_label_loss and LRSC_loss into its own globals (main_us3d.py:18) and calls them by bare name (:204-206), so the drop-in is the
     same rebinding, in the SCRIPT's module.  Returns {name: previous object} for `uninstall`."""
     from . import losses
-    previous = {}
-    for name in losses.NAMES:
-        previous[name] = getattr(script_module, name, None)
-        setattr(script_module, name, getattr(losses, name))
-    return previous
+    return _rebind(script_module, losses.NAMES, losses)
 
 
 def install_metrics(script_module):
@@ -64,11 +63,7 @@ def install_metrics(script_module):
     and SegmentationMetric by `from utils import *` (main_us3d.py:16) and call them by bare name in test_sample (:228, :254-257), so
     the drop-in is the same rebinding in the SCRIPT's module.  Returns {name: previous object} for `uninstall`."""
     from . import metrics
-    previous = {}
-    for name in metrics.NAMES:
-        previous[name] = getattr(script_module, name, None)
-        setattr(script_module, name, getattr(metrics, name))
-    return previous
+    return _rebind(script_module, metrics.NAMES, metrics)
 
 
 def install_visualization(script_module):
@@ -76,11 +71,7 @@ def install_visualization(script_module):
     `from utils import *` (main_us3d.py:16; utils/__init__.py:2, :6) and call them by bare name in test_sample (main_us3d.py:266-268),
     so the drop-in is the same rebinding in the SCRIPT's module.  Returns {name: previous object} for `uninstall`."""
     from . import visualization
-    previous = {}
-    for name in visualization.NAMES:
-        previous[name] = getattr(script_module, name, None)
-        setattr(script_module, name, getattr(visualization, name))
-    return previous
+    return _rebind(script_module, visualization.NAMES, visualization)
 
 
 def uninstall(model_module, previous):

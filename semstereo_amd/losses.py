@@ -17,37 +17,19 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import engine as E
+from ._host import LABEL_CODES, _c, count
 from ._lib import call, ptr
-from .engine import PATH_COUNTS
 
 NCLS = 6
 TRAIN_WEIGHTS = (1.0, 0.6, 0.5, 0.3)      # models/loss.py:20
 TEST_WEIGHTS = (1.0,)                     # :27
 DICE_EPS = 1e-6                           # :33
 NAMES = ("model_loss_train", "model_loss_test", "model_label_loss", "LRSC_loss")
-_LABEL_CODES = {torch.int64: 0, torch.uint8: 1, torch.float32: 2}       # include/semstereo_hip.h: label_dtype
-_WS_BYTES = {}
-
-
-def _count(hip):
-    key = "loss_hip" if hip else "loss_torch"
-    PATH_COUNTS[key] = PATH_COUNTS.get(key, 0) + 1
-
-
-def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
 
 
 def workspace_bytes(kind):
     """Scratch of the forward entry points: kind 0 = ss_disparity_loss_fwd, 1 = ss_label_loss_fwd / ss_lrsc_loss_fwd."""
-    if kind not in _WS_BYTES:
-        import ctypes
-        n = ctypes.c_longlong(0)
-        status = _lib.load().ss_loss_workspace_bytes(kind, ctypes.byref(n))
-        if status != 0:
-            raise _lib.SemStereoHipError(f"ss_loss_workspace_bytes failed ({status})")
-        _WS_BYTES[kind] = int(n.value)
-    return _WS_BYTES[kind]
+    return _lib.query_bytes("ss_loss_workspace_bytes", kind)
 
 
 def _workspace(kind, device):
@@ -189,14 +171,14 @@ class _LabelLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, disp, ignore, scale, warped):
         logits, labels = _c(logits), _c(labels)
-        if labels.dtype not in _LABEL_CODES:
+        if labels.dtype not in LABEL_CODES:
             labels = labels.to(torch.int64)
         B, C, H, W = logits.shape
         dev = logits.device
         rec = torch.empty(8, dtype=torch.float64, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         ws = _workspace(1, dev)
-        code = _LABEL_CODES[labels.dtype]
+        code = LABEL_CODES[labels.dtype]
         with torch.cuda.device(dev):
             if disp is None:
                 call("ss_label_loss_fwd", ptr(logits), ptr(labels), code, B, C, H, W, int(ignore), float(scale), ptr(rec), ptr(loss), ptr(ws),
@@ -233,9 +215,9 @@ def _disparity_loss(disp_ests, disp_gts, img_masks, rng, weights, l1):
     n = min(len(disp_ests), len(disp_gts), len(img_masks), len(weights))
     ests, gts, masks = list(disp_ests[:n]), list(disp_gts[:n]), list(img_masks[:n])
     if E.LOSS_HIP and supported_disparity(ests, gts, masks):
-        _count(True)
+        count("loss_hip")
         return _DisparityLoss.apply(weights, l1, rng, n, *ests, *gts, *masks)
-    _count(False)
+    count("loss_torch")
     return _disparity_loss_torch(ests, gts, masks, rng, weights, l1)
 
 
@@ -255,9 +237,9 @@ def model_label_loss(masks_preds, true_masks, num_classes, attention_weights_onl
         raise ValueError(f"logits {tuple(masks_preds.shape)} do not carry num_classes = {num_classes} channels")
     scale = 1.6 if attention_weights_only else 2.4
     if E.LOSS_HIP and ignore and supported_labels(masks_preds, true_masks):
-        _count(True)
+        count("loss_hip")
         return _LabelLoss.apply(masks_preds, true_masks, None, int(ignore), scale, None)
-    _count(False)
+    count("loss_torch")
     return _label_loss_torch(masks_preds, true_masks, int(ignore) if ignore else None, True, bool(ignore), scale)
 
 
@@ -267,9 +249,9 @@ def LRSC_loss(label_est_r, disp_ests, y, warped=None):
     disp = disp_ests[0]
     if E.LOSS_HIP and supported_labels(label_est_r, y, disp) and (warped is None or (
             warped.dtype == torch.int64 and warped.shape == y.shape and warped.device == y.device and warped.is_contiguous())):
-        _count(True)
+        count("loss_hip")
         return _LabelLoss.apply(label_est_r, y, disp, -1, 1.0, warped)
-    _count(False)
+    count("loss_torch")
     yw = warp_labels(disp, y)
     if warped is not None:
         warped.copy_(yw)

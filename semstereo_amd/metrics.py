@@ -26,48 +26,22 @@ import torch
 
 from . import _lib
 from . import engine as E
+from ._host import LABEL_CODES, _c, _nograd, count
 from ._lib import call, ptr
-from .engine import PATH_COUNTS
 
 NCLS = 6                                   # channels the confusion kernel is built for
 NAMES = ("EPE_metric", "D1_metric", "Thres_metric", "EPE_metric_mask", "D1_metric_mask", "Thres_metric_mask", "SegmentationMetric")
 COUNT_FIELDS = ("n_sel", "n_mask", "n_pos", "n_d1", "n_thr0", "n_thr1", "n_thr2", "n_thr3")      # record["counts"][..., i]
-_LABEL_CODES = {torch.int64: 0, torch.uint8: 1, torch.float32: 2}       # include/semstereo_hip.h: label_dtype
-_WS_BYTES = {}
 _MAPS = {}
-
-
-def _count(hip):
-    key = "metrics_hip" if hip else "metrics_torch"
-    PATH_COUNTS[key] = PATH_COUNTS.get(key, 0) + 1
-
-
-def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
 
 
 def workspace_bytes(kind):
     """Scratch of the entry points: kind 0 = ss_disparity_metrics_fwd, 1 = ss_seg_confusion_fwd."""
-    if kind not in _WS_BYTES:
-        import ctypes
-        n = ctypes.c_longlong(0)
-        status = _lib.load().ss_metrics_workspace_bytes(kind, ctypes.byref(n))
-        if status != 0:
-            raise _lib.SemStereoHipError(f"ss_metrics_workspace_bytes failed ({status})")
-        _WS_BYTES[kind] = int(n.value)
-    return _WS_BYTES[kind]
+    return _lib.query_bytes("ss_metrics_workspace_bytes", kind)
 
 
 def _workspace(kind, device):
     return torch.empty(workspace_bytes(kind) // 8 + 1, dtype=torch.int64, device=device)
-
-
-def _nograd(fn):
-    def wrapper(*args, **kwargs):
-        with torch.no_grad():
-            return fn(*args, **kwargs)
-    wrapper.__name__, wrapper.__doc__ = fn.__name__, fn.__doc__
-    return wrapper
 
 
 def _check_shapes(*ts):
@@ -161,10 +135,10 @@ def disparity_metrics(disp_ests, disp_gt, mask=None, maxdisp=None, thresholds=(1
     thresholds = tuple(float(t) for t in thresholds)
     rng = (0.0, 0.0) if maxdisp is None else (-float(maxdisp), float(maxdisp))
     if E.METRICS_HIP and len(thresholds) <= 4 and supported_disparity(ests, disp_gt, mask, mask_img):
-        _count(True)
+        count("metrics_hip")
         out, counts, sums = _disparity_hip(ests, disp_gt, mask, mask_img, rng, thresholds)
     else:
-        _count(False)
+        count("metrics_torch")
         gt = disp_gt
         ests = [e.to(gt.dtype) for e in ests]
         out, counts, sums = _disparity_torch(ests, gt, mask, mask_img, rng, thresholds)
@@ -381,9 +355,9 @@ def _nanmean(v):
 def _joint_add(logits, labels, joint):
     """joint += the joint histogram of this batch, on the kernel where it applies."""
     if E.METRICS_HIP and supported_confusion(logits, labels) and joint.is_contiguous():
-        _count(True)
+        count("metrics_hip")
         logits = _c(logits)
-        if labels.dtype not in _LABEL_CODES:
+        if labels.dtype not in LABEL_CODES:
             labels = labels.to(torch.int64)
         B, C, H, W = logits.shape
         if labels.stride(2) != 1 or labels.stride(1) < W or (B > 1 and labels.stride(0) < (H - 1) * labels.stride(1) + W):
@@ -391,10 +365,10 @@ def _joint_add(logits, labels, joint):
         image_stride = max(labels.stride(0), (H - 1) * labels.stride(1) + W)             # (the stride of a batch of one is arbitrary)
         ws = _workspace(1, logits.device)
         with torch.cuda.device(logits.device):
-            call("ss_seg_confusion_fwd", ptr(logits), ptr(labels), _LABEL_CODES[labels.dtype], B, C, H, W, labels.stride(1), image_stride,
+            call("ss_seg_confusion_fwd", ptr(logits), ptr(labels), LABEL_CODES[labels.dtype], B, C, H, W, labels.stride(1), image_stride,
                  ptr(joint), 1, ptr(ws), ws.numel() * 8)
     else:
-        _count(False)
+        count("metrics_torch")
         joint += _joint_torch(logits, labels)
 
 

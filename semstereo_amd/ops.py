@@ -11,11 +11,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import deferred as dfr
+from ._host import _c
 from ._lib import call, ptr
-
-
-def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
 
 
 def _needs_grad(*ts):

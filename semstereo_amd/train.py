@@ -21,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from ._host import _c, count
 from ._lib import call, ptr
 
 
@@ -29,17 +30,8 @@ def _M():
     return modules
 
 
-def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
-
-
 def _on(x):
     return _M().TRAIN_HIP and x.is_cuda and x.dtype == torch.float32
-
-
-def _count(kind):
-    pc = _M().PATH_COUNTS
-    pc[kind] = pc.get(kind, 0) + 1
 
 
 # ---- BatchNorm with batch statistics (+ ReLU) ---------------------------------------------------------------------------------
@@ -134,17 +126,17 @@ def batchnorm_train(bn, x, relu=False, residual=None):
     as F.batch_norm does; in eval() (frozen statistics, r05) on the running statistics as constants of the graph."""
     if (_on(x) and isinstance(bn, nn.modules.batchnorm._BatchNorm) and not bn.training and bn.running_mean is not None
             and x.shape[1] <= 65535):
-        _count("hip_train")
+        count("hip_train")
         with torch.no_grad():
             invstd = torch.rsqrt(bn.running_var.float() + bn.eps)
         return _BatchNormEval.apply(x, bn.weight, bn.bias, bn.running_mean.float(), invstd, relu, residual)
     if not (_on(x) and isinstance(bn, nn.modules.batchnorm._BatchNorm) and bn.training and x.shape[1] <= 65535):
-        _count("torch")
+        count("torch")
         y = bn(x)
         if residual is not None:
             y = y + residual
         return F.relu(y) if relu else y
-    _count("hip_train")
+    count("hip_train")
     tracked = bn.track_running_stats and bn.running_mean is not None
     if (tracked and bn.momentum is not None and bn.running_mean.dtype == torch.float32 and bn.running_var.dtype == torch.float32
             and bn.running_mean.is_contiguous() and bn.running_var.is_contiguous() and bn.running_mean.device == x.device
@@ -212,9 +204,9 @@ class _ConvK1(torch.autograd.Function):
 def conv_k1(x, weight, bias=None):
     """1x1 Conv2d / 1x1x1 Conv3d / Linear over the channel axis of [B,C,*spatial]."""
     if _on(x) and x.dim() in (4, 5):
-        _count("hip_train")
+        count("hip_train")
         return _ConvK1.apply(x, weight, bias)
-    _count("torch")
+    count("torch")
     w = weight.reshape(weight.shape[0], weight.shape[1], *([1] * (x.dim() - 2)))
     return (F.conv3d if x.dim() == 5 else F.conv2d)(x, w, bias)
 
@@ -245,12 +237,7 @@ def conv2d_k3_wgrad_applies(g, x, rem=None):
 
 
 def conv2d_k3_wgrad_workspace_bytes(B, C0, C1, H, W, Cout):
-    import ctypes
-    n = ctypes.c_longlong(0)
-    status = _lib.load().ss_conv2d_k3_wgrad_workspace_bytes(B, C0, C1, H, W, Cout, ctypes.byref(n))
-    if status != 0:
-        raise _lib.SemStereoHipError(f"ss_conv2d_k3_wgrad_workspace_bytes failed ({status})")
-    return n.value
+    return _lib.query_bytes("ss_conv2d_k3_wgrad_workspace_bytes", B, C0, C1, H, W, Cout)
 
 
 def conv2d_k3_wgrad_hip(g, x, rem=None):
@@ -266,7 +253,7 @@ def conv2d_k3_wgrad_hip(g, x, rem=None):
     work = torch.empty(conv2d_k3_wgrad_workspace_bytes(B, C0, C1, H, W, Cout) // 4, dtype=torch.float32, device=g.device)
     with torch.cuda.device(dev):
         call("ss_conv2d_k3_wgrad_fwd", ptr(g), ptr(x), ptr(rem), ptr(gw), ptr(work), B, C0, C1, H, W, Cout)
-    _count("wgrad2d")
+    count("wgrad2d")
     return gw
 
 
@@ -300,9 +287,9 @@ class _Conv2dK3(torch.autograd.Function):
 def conv2d_k3(conv, x):
     M = _M()
     if _on(x) and M._is_plain_3x3(conv):
-        _count("hip_train")
+        count("hip_train")
         return _Conv2dK3.apply(x, conv.weight)
-    _count("torch")
+    count("torch")
     return conv(x)
 
 
@@ -341,9 +328,9 @@ class _DepthwisePatch(torch.autograd.Function):
 
 def depthwise_patch(conv, x):
     if _on(x) and x.dim() == 5:
-        _count("hip_train")
+        count("hip_train")
         return _DepthwisePatch.apply(x, conv.weight)
-    _count("torch")
+    count("torch")
     return nn.Conv3d.forward(conv, x)
 
 
@@ -375,9 +362,9 @@ class _ChannelGate(torch.autograd.Function):
 
 def channel_gate(att_logits, cv):
     if _on(cv):
-        _count("hip_train")
+        count("hip_train")
         return _ChannelGate.apply(att_logits, cv)
-    _count("torch")
+    count("torch")
     return torch.sigmoid(att_logits).unsqueeze(2) * cv
 
 
@@ -424,7 +411,7 @@ def window_attention(x, qkv_linear, final_conv, heads, block):
     """attention_block.forward (models/submodule_other.py:790-837): the qkv projection and final1x1 as 1x1x1 convolutions with bias
     over the REAL positions, the attention core per (window, head) -- pad tokens of volumes whose H, W are not window multiples
     carry the Linear's bias as their q / k / v (r04: forward and backward)."""
-    _count("hip_train")
+    count("hip_train")
     qkv = conv_k1(x, qkv_linear.weight, qkv_linear.bias)
     y = _WindowAttentionCore.apply(qkv, qkv_linear.bias, heads, tuple(block))
     return conv_k1(y, final_conv.weight, final_conv.bias)
@@ -540,7 +527,7 @@ def attention_tail_applies(cost_att, rng, H, W, left=None, right=None, k=None):
 def attention_tail(cost_att, left, right, gamma, beta, rng, H, W, k):
     """models/SemStereo.py:279-310 with autograd on: three HIP forward launches, three HIP backward launches.
     -> (att_topk [B,1,k,H,W], samples [B,k,H,W], pred_att [B,H,W], pred0 [B,H,W])."""
-    _count("hip_train")
+    count("hip_train")
     att_weights, pred0, var = _UpsampleSoftmaxRegression.apply(cost_att, H, W, tuple(rng))
     strength = _SampleStrength.apply(left, right, pred0, var, gamma, beta)
     att_topk, samples, pred_att = _TopkCandidates.apply(att_weights, strength, k, tuple(rng))
@@ -600,5 +587,5 @@ def concat_volume_applies(left, right, samples, att):
 def concat_volume_sampled(left, right, samples, att, margin=64):
     """models/SemStereo.py:316-318 under autograd -> [B, 2C, nd, H, W].  `margin`: the |candidate| the backward's LDS windows cover
     (maxdisp / 4 of the caller: a hint, larger shifts are still summed, one atomic at a time)."""
-    _count("hip_train")
+    count("hip_train")
     return _ConcatVolumeSampled.apply(left, right, samples, att, margin)

@@ -23,15 +23,13 @@ layers in every round at both measured batch sizes (profiles/EXPERIMENTS.md sect
 In train() the reference calls each Conv2x of FeatUp on the left view and then on the right view, each with its own batch statistics,
 the running statistics moving twice in that order (models/SemStereo.py:74-84): the twins call conv2x_train per view, never per pair.
 """
-import ctypes
-
 import torch
-import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import engine as E
 from . import train as T
+from ._host import bn_ok, count
 from ._lib import ptr
 
 #: the two gradient seams of `_Deconv2dK4S2`: False sends that gradient to aten.convolution_backward (the other keeps its kernel)
@@ -45,14 +43,9 @@ def _enabled(*xs):
                     and x.numel() > 0 for x in xs))
 
 
-def _bn_ok(bn):
-    return isinstance(bn, nn.BatchNorm2d) and (bn.training or bn.running_mean is not None)
-
-
 def _count():
-    pc = E.PATH_COUNTS
-    pc["hip_train"] = pc.get("hip_train", 0) + 1
-    pc["decoder_train"] = pc.get("decoder_train", 0) + 1
+    count("hip_train")
+    count("decoder_train")
 
 
 def pack_conv2d_k4s2_weight(w):
@@ -80,11 +73,7 @@ def conv2d_k4s2_hip(g, wsplit, Cout):
 
 
 def wgrad_workspace_bytes(B, Cin, H, W, Cout):
-    n = ctypes.c_longlong(0)
-    status = _lib.load().ss_deconv2d_k4s2_wgrad_workspace_bytes(B, Cin, H, W, Cout, ctypes.byref(n))
-    if status != 0:
-        raise _lib.SemStereoHipError(f"ss_deconv2d_k4s2_wgrad_workspace_bytes failed ({status})")
-    return n.value
+    return _lib.query_bytes("ss_deconv2d_k4s2_wgrad_workspace_bytes", B, Cin, H, W, Cout)
 
 
 def deconv2d_k4s2_wgrad_hip(x, g, Cout):
@@ -191,7 +180,7 @@ def _deconv_fits(conv, x):
 def conv2x_train_applies(m, x, rem):
     a, b = m.conv1, m.conv2
     return (_enabled(x, rem) and m.concat and not m.is_3d and _deconv_fits(a.conv, x) and a.conv.bias is None and a.use_bn and a.relu
-            and E._is_plain_3x3(b.conv) and b.use_bn and _bn_ok(a.bn) and _bn_ok(b.bn)
+            and E._is_plain_3x3(b.conv) and b.use_bn and bn_ok(a.bn) and bn_ok(b.bn)
             and a.conv.out_channels % 8 == 0 and b.conv.in_channels == a.conv.out_channels + rem.shape[1]
             and tuple(rem.shape) == (x.shape[0], rem.shape[1], 2 * x.shape[2], 2 * x.shape[3])      # (else: the F.interpolate branch)
             and b.conv.in_channels * rem.shape[2] * rem.shape[3] * 4 < 0x7fffffff)

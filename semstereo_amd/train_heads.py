@@ -11,15 +11,13 @@ not built for -- the geometry conditions of engine.seghead_applies / engine.run_
 non-contiguous inputs -- and a projection of fewer than `PROJ_MIN_POSITIONS` positions (measured slower than the stock layers in
 every round there) keep the stock layers (`*_applies` below is False; the twins count PATH_COUNTS["torch"]).
 """
-import ctypes
-
 import torch
-import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import engine as E
 from . import train as T
+from ._host import bn_ok, count
 from ._lib import ptr
 
 #: a projection runs the kernels from this many positions (B * H * W) up.  Below it a training call -- two weight packings, six small
@@ -35,16 +33,9 @@ def _enabled(x):
             and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous())
 
 
-def _bn_ok(bn):
-    return isinstance(bn, nn.BatchNorm2d) and (bn.training or bn.running_mean is not None)
-
-
 def tail_workspace(B, C, H, W, device):
-    n = ctypes.c_longlong(0)
-    status = _lib.load().ss_seghead_tail_workspace_bytes(B, 32, C, H, W, ctypes.byref(n))
-    if status != 0:
-        raise _lib.SemStereoHipError(f"ss_seghead_tail_workspace_bytes failed ({status})")
-    return torch.empty(max(1, n.value // 4), dtype=torch.float32, device=device)
+    n = _lib.query_bytes("ss_seghead_tail_workspace_bytes", B, 32, C, H, W)
+    return torch.empty(max(1, n // 4), dtype=torch.float32, device=device)
 
 
 # ---- the head's tail: Conv2d(32 -> C, 1x1, bias) + bilinear x2 ----------------------------------------------------------------
@@ -89,7 +80,7 @@ class _SegheadTail(torch.autograd.Function):
 
 def seghead_train_applies(head, x):
     # (the tail addresses one element's 32-channel map and its up-sampled logits through 32-bit offsets: its own size condition)
-    return (_enabled(x) and E.seghead_applies(head, x) and _bn_ok(head.conv1.bn)
+    return (_enabled(x) and E.seghead_applies(head, x) and bn_ok(head.conv1.bn)
             and 32 * x.shape[2] * x.shape[3] * 4 < 0x7fffffff
             and head.conv2.out_channels * (4 if head.scale_factor is not None else 1) * x.shape[2] * x.shape[3] * 4 < 0x7fffffff)
 
@@ -97,7 +88,7 @@ def seghead_train_applies(head, x):
 def seghead_train(head, x):
     """segmenthead.forward under autograd / in train(): 3x3 conv, BatchNorm (batch statistics in train(), frozen ones in eval()) +
     ReLU, then the tail."""
-    T._count("hip_train")
+    count("hip_train")
     a = T.conv2d_k3(head.conv1.conv, x)
     a = T.batchnorm_train(head.conv1.bn, a, relu=True)
     return _SegheadTail.apply(a, head.conv2.weight, head.conv2.bias, head.scale_factor is not None)
@@ -146,10 +137,10 @@ def proj_train_applies(proj, x):
     return (_enabled(x) and E._is_conv_k1(conv) and conv.in_channels % 8 == 0 and conv.out_channels % 8 == 0
             and x.shape[1] == conv.in_channels and x.numel() > 0
             and x.shape[0] * x.shape[2] * x.shape[3] >= PROJ_MIN_POSITIONS
-            and max(conv.in_channels, conv.out_channels) * x.shape[2] * x.shape[3] * 4 < 0x7fffffff and _bn_ok(bn))
+            and max(conv.in_channels, conv.out_channels) * x.shape[2] * x.shape[3] * 4 < 0x7fffffff and bn_ok(bn))
 
 
 def proj_train(proj, x):
     """nn.Sequential(Conv2d(1x1, bias), BatchNorm2d) under autograd / in train()."""
-    T._count("hip_train")
+    count("hip_train")
     return T.batchnorm_train(proj[1], _Proj2dK1.apply(x, proj[0].weight, proj[0].bias), relu=False)

@@ -10,15 +10,12 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._host import _c
 from ._lib import call, ptr
 
 NCLS = 6
 SAVED_FLOATS = 256        # csrc/ssr_upsample_train.hip: SAVED_FLOATS
 _KS, _GMAX = 128, 1024    # ... KS (slab row, doubles) and GMAX (workgroups of a reduction pass)
-
-
-def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
 
 
 def _bns(m):

@@ -24,26 +24,21 @@ Departures from the reference, on both paths:
   * `normalize_image` is (clamp(x, lo, hi) - lo) / max(hi - lo, 1e-5) in fp32 throughout.  make_grid forms `hi - lo` in double before
     it divides; the divisor differs by at most one ulp.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
 from . import engine as E
+from ._host import LABEL_CODES, _c, _const, _nograd, count
 from ._lib import call, ptr
-from .engine import PATH_COUNTS
 from .metrics import argmax_first
 
 NCLS = 6                                   # classes of the palette and channels the kernel takes
 NAMES = ("disp_error_image_func", "feature_vis")        # what install_visualization rebinds
-_LABEL_CODES = {torch.int64: 0, torch.uint8: 1, torch.float32: 2}       # include/semstereo_hip.h: src_dtype (-1: logits)
 _OUT_CODES = {torch.float32: 0, torch.uint8: 1}
 _MAX_QUADS = 2 ** 31 - 1
 #: utils/mask_vis.py:10-15
 PALETTE = ((0, 0, 0), (255, 0, 0), (0, 255, 0), (0, 0, 255), (255, 255, 0), (0, 255, 255))
-_WS_BYTES = []
-_CONST = {}
 
 
 def gen_error_colormap():
@@ -61,40 +56,9 @@ def gen_error_colormap():
 error_colormap = gen_error_colormap()
 
 
-def _count(hip, n=1):
-    key = "vis_hip" if hip else "vis_torch"
-    PATH_COUNTS[key] = PATH_COUNTS.get(key, 0) + n
-
-
-def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _nograd(fn):
-    def wrapper(*args, **kwargs):
-        with torch.no_grad():
-            return fn(*args, **kwargs)
-    wrapper.__name__, wrapper.__doc__ = fn.__name__, fn.__doc__
-    return wrapper
-
-
 def workspace_bytes():
     """Scratch of ss_image_minmax_fwd."""
-    if not _WS_BYTES:
-        n = ctypes.c_longlong(0)
-        status = _lib.load().ss_vis_workspace_bytes(0, ctypes.byref(n))
-        if status != 0:
-            raise _lib.SemStereoHipError(f"ss_vis_workspace_bytes failed ({status})")
-        _WS_BYTES.append(int(n.value))
-    return _WS_BYTES[0]
-
-
-def _const(key, device, make):
-    """A small constant tensor on `device`, uploaded once (without waiting)."""
-    k = (key, str(device))
-    if k not in _CONST:
-        _CONST[k] = make().to(device, non_blocking=True)
-    return _CONST[k]
+    return _lib.query_bytes("ss_vis_workspace_bytes", 0)
 
 
 def _fits(B, H, W):
@@ -149,7 +113,7 @@ def disp_error_image(D_est_tensor, D_gt_tensor, abs_thres=3., rel_thres=0.05, di
     assert gt.dim() == 3 and est.shape == gt.shape
     lo, hi = float(valid_range[0]), float(valid_range[1])
     if E.VIS_HIP and supported_error_image(est, gt):
-        _count(True)
+        count("vis_hip")
         est, gt = _c(est), _c(gt)
         B, H, W = gt.shape
         out = torch.empty((B, 3, H, W), dtype=torch.float32, device=gt.device)
@@ -157,7 +121,7 @@ def disp_error_image(D_est_tensor, D_gt_tensor, abs_thres=3., rel_thres=0.05, di
             call("ss_disp_error_image_fwd", ptr(est), ptr(gt), _TABLE.ctypes.data, B, H, W, float(abs_thres), float(rel_thres), int(bool(legend)),
                  int(bool(signed)), lo, hi, ptr(out))
         return out
-    _count(False)
+    count("vis_torch")
     if est.dtype != gt.dtype:
         est = est.to(gt.dtype)
     return _error_image_torch(est, gt, float(abs_thres), float(rel_thres), legend, signed, lo, hi)
@@ -209,9 +173,9 @@ def feature_vis(feats, dtype=torch.float32):
     assert feats.dim() == 4 and dtype in _OUT_CODES
     B, C, H, W = feats.shape
     if E.VIS_HIP and feats.is_cuda and feats.dtype == torch.float32 and C <= NCLS and _fits(B, H, W):
-        _count(True)
+        count("vis_hip")
         return _color_hip(_c(feats), -1, B, C, H, W, W, H * W, dtype)
-    _count(False)
+    count("vis_torch")
     cls = argmax_first(feats)
     return _colours_torch(torch.where(cls < NCLS, cls, torch.full_like(cls, NCLS)), dtype)
 
@@ -223,13 +187,13 @@ def label_vis(labels, dtype=torch.float32):
     assert labels.dim() == 3 and dtype in _OUT_CODES
     B, H, W = labels.shape
     if E.VIS_HIP and labels.is_cuda and not labels.is_complex() and _fits(B, H, W):
-        _count(True)
-        y = labels if labels.dtype in _LABEL_CODES else labels.to(torch.int64)
+        count("vis_hip")
+        y = labels if labels.dtype in LABEL_CODES else labels.to(torch.int64)
         if y.stride(2) != 1 or y.stride(1) < W or (B > 1 and y.stride(0) < (H - 1) * y.stride(1) + W):
             y = y.contiguous()
         image_stride = max(y.stride(0), (H - 1) * y.stride(1) + W)                 # (the stride of a batch of one is arbitrary)
-        return _color_hip(y, _LABEL_CODES[y.dtype], B, NCLS, H, W, y.stride(1), image_stride, dtype)
-    _count(False)
+        return _color_hip(y, LABEL_CODES[y.dtype], B, NCLS, H, W, y.stride(1), image_stride, dtype)
+    count("vis_torch")
     return _colours_torch(_label_classes(labels), dtype)
 
 
@@ -252,7 +216,7 @@ def normalize_image(x):
     assert x.dim() == 4
     B, C, H, W = x.shape
     if E.VIS_HIP and x.is_cuda and x.dtype == torch.float32 and 0 < B <= 1024 and x[0].numel() > 0:
-        _count(True)
+        count("vis_hip")
         x = _c(x)
         minmax = torch.empty((B, 2), dtype=torch.float32, device=x.device)
         ws = torch.empty(workspace_bytes() // 4, dtype=torch.float32, device=x.device)
@@ -261,7 +225,7 @@ def normalize_image(x):
             call("ss_image_minmax_fwd", ptr(x), B, C * H * W, ptr(minmax), ptr(ws), ws.numel() * 4)
             call("ss_image_normalize_fwd", ptr(x), ptr(minmax), ptr(out), B, C, H * W)
         return out
-    _count(False)
+    count("vis_torch")
     return _normalize_torch(x if x.is_floating_point() else x.float())
 
 

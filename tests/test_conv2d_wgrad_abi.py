@@ -3,9 +3,9 @@ arities, refuse bad arguments before any device call, the workspace size is the 
 and off by default (no GPU needed)."""
 import ctypes
 import os
-import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi import HEADER, ROOT, declared, library
+
 NAMES = ("ss_conv2d_k3_wgrad_fwd", "ss_conv2d_k3_wgrad_workspace_bytes")
 LL = ctypes.c_longlong
 # (B, C0, C1, H, W, Cout) of the layers at 1024 x 1024 inputs, batch 4: the four Conv2x.conv2, concat_feature's two convs, segmenthead.conv1
@@ -13,30 +13,14 @@ MODEL_SHAPES = ((4, 384, 384, 64, 64, 768), (4, 256, 256, 128, 128, 512), (4, 12
                 (4, 128, 0, 256, 256, 64), (4, 64, 0, 256, 256, 32), (4, 128, 0, 512, 512, 32))
 
 
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "semstereo_hip.h")).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"int\s+(ss_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip()])
-    return out
-
-
-def _lib():
-    import __graft_entry__ as ge
-    from semstereo_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib, _lib.load()
-
-
 def test_entry_points_are_declared_with_the_bindings_arities():
-    from semstereo_amd import _lib as _l
-    decl = _declared()
+    _l, lib = library()
+    decl = {name: len(params) for name, (_, params) in declared().items()}
     for name in NAMES:
-        assert name in decl and name in _l.EXPORTS, name
-    assert NAMES[0] in _l._SIGNATURES and len(_l._SIGNATURES[NAMES[0]]) == decl[NAMES[0]] == 12
-    assert decl[NAMES[1]] == 7
-    header = open(os.path.join(ROOT, "include", "semstereo_hip.h")).read()
+        assert name in decl and name in _l._SIGNATURES and name in _l.EXPORTS, name
+    assert len(_l._SIGNATURES[NAMES[0]]) == decl[NAMES[0]] == 12
+    assert len(_l._SIGNATURES[NAMES[1]]) == decl[NAMES[1]] == 7
+    header = open(HEADER).read()
     for cite in ("models/submodule.py:142, 157-160", "models/SemStereo.py:221-223", "models/submodule.py:40-52"):
         assert cite in header, cite
     mk = open(os.path.join(ROOT, "semstereo_amd", "csrc", "Makefile")).read()
@@ -44,7 +28,7 @@ def test_entry_points_are_declared_with_the_bindings_arities():
 
 
 def test_the_library_exports_them_and_the_abi_version_is_unchanged():
-    _l, lib = _lib()
+    _l, lib = library()
     for name in NAMES:
         assert hasattr(lib, name), name
     assert len(lib.ss_conv2d_k3_wgrad_fwd.argtypes) == 12 and len(lib.ss_conv2d_k3_wgrad_workspace_bytes.argtypes) == 7
@@ -52,7 +36,7 @@ def test_the_library_exports_them_and_the_abi_version_is_unchanged():
 
 
 def test_bad_arguments_are_refused_before_any_device_call():
-    _l, lib = _lib()
+    _l, lib = library()
     buf = (ctypes.c_double * 64)()
     p = ctypes.cast(buf, ctypes.c_void_p)                      # host memory that is never followed
 
@@ -81,7 +65,7 @@ def _formula(B, C0, C1, H, W, Cout):
 
 
 def test_workspace_bytes_is_the_documented_formula():
-    _l, lib = _lib()
+    _l, lib = library()
     n = LL(-1)
     ws = lib.ss_conv2d_k3_wgrad_workspace_bytes
     ref = ctypes.byref(n)

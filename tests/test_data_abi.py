@@ -6,30 +6,15 @@ import re
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi import ROOT, declared, library
+
 NAMES = ("ss_prep_views_fwd", "ss_prep_pyramid_fwd", "ss_prep_luma_stats_fwd", "ss_prep_gradients_fwd")      # (a stream argument each)
 QUERY = "ss_prep_workspace_bytes"
 
 
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "semstereo_hip.h")).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"int\s+(ss_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip()])
-    return out
-
-
-def _lib():
-    import __graft_entry__ as ge
-    from semstereo_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib, _lib.load()
-
-
 def test_prep_entry_points_are_declared_bound_and_exported():
-    _l, lib = _lib()
-    decl = _declared()
+    _l, lib = library()
+    decl = {name: len(params) for name, (_, params) in declared().items()}
     for name in NAMES:
         assert name in decl and name in _l._SIGNATURES and name in _l.EXPORTS, name
         assert len(_l._SIGNATURES[name]) == decl[name], (name, len(_l._SIGNATURES[name]), decl[name])
@@ -47,7 +32,7 @@ def test_the_source_only_launches():
 
 
 def test_bad_arguments_are_refused_before_any_device_call():
-    _l, lib = _lib()
+    _l, lib = library()
     n = ctypes.c_longlong(0)
     q = lib.ss_prep_workspace_bytes
     assert q(1, 4, 4, None) == -1 and q(0, 4, 4, ctypes.byref(n)) == -1 and q(1, 0, 4, ctypes.byref(n)) == -1 and q(1, 4, -1, ctypes.byref(n)) == -1

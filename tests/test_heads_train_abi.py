@@ -2,36 +2,18 @@
 arities, refuse bad arguments before any device call, and the opt-in switch is off by default (no GPU needed)."""
 import ctypes
 import os
-import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi import ROOT, declared, library
+
 NAMES = ("ss_seghead_tail_fwd", "ss_seghead_tail_bwd", "ss_seghead_tail_workspace_bytes")
 LL = ctypes.c_longlong
 
 
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "semstereo_hip.h")).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"int\s+(ss_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip()])
-    return out
-
-
-def _lib():
-    import __graft_entry__ as ge
-    from semstereo_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib, _lib.load()
-
-
 def test_tail_entry_points_are_declared_with_the_bindings_arities():
-    from semstereo_amd import _lib as _l
-    decl = _declared()
+    _l, lib = library()
+    decl = {name: len(params) for name, (_, params) in declared().items()}
     for name in NAMES:
-        assert name in decl and name in _l.EXPORTS, name
-    for name in NAMES[:2]:
-        assert name in _l._SIGNATURES
+        assert name in decl and name in _l._SIGNATURES and name in _l.EXPORTS, name
         assert len(_l._SIGNATURES[name]) == decl[name], (name, len(_l._SIGNATURES[name]), decl[name])
     assert decl["ss_seghead_tail_fwd"] == 11 and decl["ss_seghead_tail_bwd"] == 14 and decl["ss_seghead_tail_workspace_bytes"] == 6
     mk = open(os.path.join(ROOT, "semstereo_amd", "csrc", "Makefile")).read()
@@ -39,7 +21,7 @@ def test_tail_entry_points_are_declared_with_the_bindings_arities():
 
 
 def test_the_library_exports_them_and_the_abi_version_is_unchanged():
-    _l, lib = _lib()
+    _l, lib = library()
     for name in NAMES:
         assert hasattr(lib, name), name
     assert len(lib.ss_seghead_tail_workspace_bytes.argtypes) == 6
@@ -47,7 +29,7 @@ def test_the_library_exports_them_and_the_abi_version_is_unchanged():
 
 
 def test_bad_arguments_are_refused_before_any_device_call():
-    _l, lib = _lib()
+    _l, lib = library()
     buf = (ctypes.c_double * 64)()
     p = ctypes.cast(buf, ctypes.c_void_p)                      # 16-byte aligned host memory that is never followed
 

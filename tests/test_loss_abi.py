@@ -1,35 +1,18 @@
 """CPU: the objective's entry points (csrc/loss.hip) are declared, bound and exported with matching arities, refuse NULL arguments
 before any device call, and CPU tensors take the PyTorch composition (no GPU needed)."""
 import ctypes
-import os
-import re
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi import declared, library
+
 NAMES = ("ss_loss_workspace_bytes", "ss_disparity_loss_fwd", "ss_disparity_loss_bwd", "ss_label_loss_fwd", "ss_label_loss_bwd",
          "ss_lrsc_loss_fwd", "ss_lrsc_loss_bwd")
 
 
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "semstereo_hip.h")).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"int\s+(ss_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip()])
-    return out
-
-
-def _lib():
-    import __graft_entry__ as ge
-    from semstereo_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib, _lib.load()
-
-
 def test_loss_entry_points_are_declared_bound_and_exported():
-    _l, lib = _lib()
-    decl = _declared()
+    _l, lib = library()
+    decl = {name: len(params) for name, (_, params) in declared().items()}
     for name in NAMES:
         assert name in decl and name in _l._SIGNATURES and name in _l.EXPORTS, name
         assert len(_l._SIGNATURES[name]) == decl[name], (name, len(_l._SIGNATURES[name]), decl[name])
@@ -38,7 +21,7 @@ def test_loss_entry_points_are_declared_bound_and_exported():
 
 
 def test_null_arguments_are_refused_before_any_device_call():
-    _l, lib = _lib()
+    _l, lib = library()
     term = [None, None, None, 16]
     assert lib.ss_disparity_loss_fwd(*(term * 4), 1.0, 0.6, 0.5, 0.3, -32.0, 32.0, 4, 0, None, None, None, 1 << 20, None) == -1
     assert lib.ss_disparity_loss_bwd(*(([None] * 4 + [16]) * 4), 1.0, 0.6, 0.5, 0.3, -32.0, 32.0, 4, 0, None, None, None) == -1

@@ -1,35 +1,18 @@
 """CPU: the evaluation metrics' entry points (csrc/metrics.hip) are declared, bound and exported with matching arities, refuse bad
 arguments before any device call, and CPU tensors take the PyTorch composition (no GPU needed)."""
 import ctypes
-import os
-import re
 import types
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi import declared, library
+
 NAMES = ("ss_metrics_workspace_bytes", "ss_disparity_metrics_fwd", "ss_seg_confusion_fwd")
 
 
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "semstereo_hip.h")).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"int\s+(ss_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip()])
-    return out
-
-
-def _lib():
-    import __graft_entry__ as ge
-    from semstereo_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib, _lib.load()
-
-
 def test_metric_entry_points_are_declared_bound_and_exported():
-    _l, lib = _lib()
-    decl = _declared()
+    _l, lib = library()
+    decl = {name: len(params) for name, (_, params) in declared().items()}
     for name in NAMES:
         assert name in decl and name in _l._SIGNATURES and name in _l.EXPORTS, name
         assert len(_l._SIGNATURES[name]) == decl[name], (name, len(_l._SIGNATURES[name]), decl[name])
@@ -38,7 +21,7 @@ def test_metric_entry_points_are_declared_bound_and_exported():
 
 
 def test_bad_arguments_are_refused_before_any_device_call():
-    _l, lib = _lib()
+    _l, lib = library()
     big = 1 << 22
     thr = (1.0, 2.0, 3.0, 4.0)
     assert lib.ss_metrics_workspace_bytes(0, None) == -1

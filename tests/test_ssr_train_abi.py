@@ -1,29 +1,15 @@
 """CPU: the SSR_upsample training entry points (csrc/ssr_upsample_train.hip) are declared, bound and exported with matching arities,
 and CPU tensors keep the PyTorch composition (no GPU needed)."""
-import os
-import re
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi import declared, library
+
 NAMES = ("ss_ssr_upsample_train_fwd", "ss_ssr_upsample_train_bwd")
 
 
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "semstereo_hip.h")).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"int\s+(ss_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S):
-        out[m.group(1)] = len([a for a in m.group(2).split(",") if a.strip()])
-    return out
-
-
 def test_training_entry_points_are_declared_bound_and_exported():
-    import __graft_entry__ as ge
-    from semstereo_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    lib = _lib.load()
-    decl = _declared()
+    _lib, lib = library()
+    decl = {name: len(params) for name, (_, params) in declared().items()}
     for name in NAMES:
         assert name in decl and name in _lib._SIGNATURES and name in _lib.EXPORTS, name
         assert len(_lib._SIGNATURES[name]) == decl[name], (name, len(_lib._SIGNATURES[name]), decl[name])
