@@ -157,10 +157,15 @@ int ss_stem_left_fused_fwd(const float* left, const void* wsplit, const float* a
  * them from the accumulator registers (no Q tile in LDS).  C = Cout = 32, nd in {6, 24, 32}; anything else is
  * SS_ERR_UNSUPPORTED.  wsplit = ss_pack_stem_left_weights_f16s of the left-half weights w [Cout, C, 27] (tap = kd*9+kh*3+kw):
  * 73728 fp16 terms in fragment order (two terms of w / u, u a power of two per (tap, output channel)) followed by the 864
- * floats u; 150912 bytes, 16-byte aligned. */
+ * floats u; ss_pack_stem_left_weights_f16s_bytes, 16-byte aligned. */
 int ss_stem_left_mfma_fwd(const float* left, const void* wsplit, const float* att, float* out, int B, int C,
                           int Cout, int nd, int H, int W, ss_stream_t stream);
 int ss_pack_stem_left_weights_f16s(const float* w, void* wsplit, int Cout, int C, ss_stream_t stream);
+/* Packed-weight sizes.  Every ss_pack_* entry point that fills a `void*` buffer of split fragments has a twin `<name>_bytes(<its
+ * scalar arguments, same order>, long long* bytes)`: the bytes the pack writes and its consumer reads, from the one function in the
+ * .hip file that owns the layout -- what a caller allocates.  No stream, no device.  A NULL `bytes` or a non-positive dimension:
+ * SS_ERR_INVALID; arguments the pack refuses: the pack's own status; a refused call writes nothing. */
+int ss_pack_stem_left_weights_f16s_bytes(int Cout, int C, long long* bytes);
 /* Fused form of models/SemStereo.py:291-292: mean over channels of left * warp(right):
  * x,y [B,C,H,W], disp [B,nd,H,W] -> [B,nd,H,W] */
 int ss_warp_correlation_fwd(const float* x, const float* y, const float* disp, float* out,
@@ -321,8 +326,9 @@ int ss_conv3d_presplit_fwd(const void* xs, const int* xexp, const void* wsplit, 
                            const float* shift, const float* gate, float* out, int B, int Cin, int D, int H, int W,
                            int Cout, int relu, ss_stream_t stream);
 /* Conv3d weight [Cout,Cin,3,3,3] fp32 -> split/packed bf16 fragments
- * [ceil(Cin/8)][14 tap pairs][3 terms][2 halves][Cout][8] (ceil(Cin/8)*14*3*2*Cout*16 bytes). */
+ * [ceil(Cin/8)][14 tap pairs][3 terms][2 halves][Cout][8] (ss_pack_conv3d_weights_bf16s_bytes). */
 int ss_pack_conv3d_weights_bf16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);
+int ss_pack_conv3d_weights_bf16s_bytes(int Cout, int Cin, long long* bytes);
 /* The two-term fp16 form of the same layers (same reference lines): ss_conv3d_bf16s_fwd / _partial_fwd with
  * nterms = 19 ("f16x3": hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_f16, half the matrix-core time of nterms = 6).
  * fp16 has 5 exponent bits, so the operands are block floating point: this packer scales each output channel's weights
@@ -330,11 +336,12 @@ int ss_pack_conv3d_weights_bf16s(const float* w, void* wsplit, int Cout, int Cin
  * of its halo tile by a power of two taken from the tile's running |max| and rescales its fp32 accumulators when it
  * changes.  Error vs exact: representation <= 2^-23 per operand + the dropped lo*lo <= 2^-22 per product, i.e. below
  * the fp32 accumulation error of any K >= 64 (measured in DESIGN.md section 4).  wsplit:
- * [ceil(Cin/8)][14][2 terms][2 halves][Cout][8] fp16 + float[Cout]  (ceil(Cin/8)*14*2*2*Cout*16 + 4*Cout bytes). */
+ * [ceil(Cin/8)][14][2 terms][2 halves][Cout][8] fp16 + float[Cout]  (ss_pack_conv3d_weights_f16s_bytes). */
 int ss_pack_conv3d_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);
+int ss_pack_conv3d_weights_f16s_bytes(int Cout, int Cin, long long* bytes);
 /* The 2-D form of the split-bf16 conv: Conv2d(k3, s1, p1, bias=False) + affine (+residual) + ReLU on [B,Cin,H,W] maps
  * (concat_feature, models/SemStereo.py:222-226): out [B,Cout,H,W]; w [Cout,Cin,3,3] -> wsplit
- * [ceil(Cin/8)][5 tap pairs][3 terms][2 halves][Cout][8] (ceil(Cin/8)*5*3*2*Cout*16 bytes). */
+ * [ceil(Cin/8)][5 tap pairs][3 terms][2 halves][Cout][8] (ss_pack_conv2d_weights_bf16s_bytes). */
 int ss_conv2d_bf16s_fwd(const float* in, const void* wsplit, const float* scale, const float* shift,
                         const float* residual, float* out, int B, int Cin, int H, int W, int Cout, int relu,
                         int nterms, ss_stream_t stream);
@@ -344,6 +351,7 @@ int ss_conv2d_bf16s_fwd(const float* in, const void* wsplit, const float* scale,
 int ss_conv2d_bf16s_pair_fwd(const float* in_a, const float* in_b, const void* wsplit, const float* scale, const float* shift,
                              float* out, int B, int Cin, int H, int W, int Cout, int relu, int nterms, ss_stream_t stream);
 int ss_pack_conv2d_weights_bf16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);
+int ss_pack_conv2d_weights_bf16s_bytes(int Cout, int Cin, long long* bytes);
 /* The same layer with its input given as TWO channel ranges: channels [0, Csplit) from x_a [B,Csplit,H,W], [Csplit, Cin) from
  * rem_a [B,Cin-Csplit,H,W] -- Conv2x's `torch.cat((x, rem), 1)` + conv2 (models/submodule.py:156-160) without the concatenated
  * tensor.  x_b / rem_b (both or neither): a second view in the same launch (FeatUp applies each Conv2x to the left view, then to the
@@ -371,9 +379,9 @@ int ss_deconv2d_bf16s_pair_fwd(const float* in_a, const float* in_b, const void*
                                float* out, int B, int Cin, int H, int W, int Cout, int relu, int nterms, ss_stream_t stream);
 /* nn.ConvTranspose2d weight [Cin,Cout,4,4] fp32 (models/submodule.py:104) -> the fragments of ss_deconv2d_bf16s_fwd:
  * [ceil(Cin/8)][ceil(Cout/32)][4 parity classes][2 tap rows][2 terms][2 tap columns][32 channels][8] fp16 of w scaled per output
- * channel by a power of two, + float[32 ceil(Cout/32)] of the inverse scales:
- * ceil(Cin/8) * ceil(Cout/32) * 16384 + 128 * ceil(Cout/32) bytes, 16-byte aligned. */
+ * channel by a power of two, + float[32 ceil(Cout/32)] of the inverse scales (ss_pack_deconv2d_weights_f16s_bytes), 16-byte aligned. */
 int ss_pack_deconv2d_weights_f16s(const float* w, void* wsplit, int Cin, int Cout, ss_stream_t stream);
+int ss_pack_deconv2d_weights_f16s_bytes(int Cin, int Cout, long long* bytes);
 /* (training) The data gradient of ConvTranspose2d(k = 4, s = 2, p = 1) -- conv1 of every 2-D Conv2x (models/submodule.py:104,
  * 136-138, 150) and `spx2` (models/SemStereo.py:207) -- as what it is: Conv2d(Cin, Cout, 4, stride=2, padding=1, bias=False) on
  * in [B,Cin,H,W] (the gradient of the transposed conv's output; H and W even, else SS_ERR_UNSUPPORTED) -> out [B,Cout,H/2,W/2], the
@@ -384,9 +392,9 @@ int ss_pack_deconv2d_weights_f16s(const float* w, void* wsplit, int Cin, int Cou
 int ss_conv2d_k4s2_f16s_fwd(const float* in, const void* wsplit, float* out, int B, int Cin, int H, int W, int Cout, ss_stream_t stream);
 /* Conv2d weight [Cout,Cin,4,4] fp32 (= nn.ConvTranspose2d's [its Cin, its Cout, 4, 4], models/submodule.py:104) -> the fragments of
  * ss_conv2d_k4s2_f16s_fwd: [ceil(Cin/8)][ceil(Cout/32)][8 K-steps][2 terms][2 lane halves][32 channels][8] fp16 of w scaled per output
- * channel by a power of two, + float[32 ceil(Cout/32)] of the inverse scales:
- * ceil(Cin/8) * ceil(Cout/32) * 16384 + 128 * ceil(Cout/32) bytes, 16-byte aligned. */
+ * channel by a power of two, + float[32 ceil(Cout/32)] of the inverse scales (ss_pack_conv2d_k4s2_weights_f16s_bytes), 16-byte aligned. */
 int ss_pack_conv2d_k4s2_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);
+int ss_pack_conv2d_k4s2_weights_f16s_bytes(int Cout, int Cin, long long* bytes);
 /* (training) The weight gradient of the same layer (models/submodule.py:104, 136-138, 150; models/SemStereo.py:207):
  * grad_w[ci,co,kh,kw] = sum_{b,y,x} in[b,ci,y,x] * grad_out[b,co,2y-1+kh,2x-1+kw], in [B,Cin,H,W], grad_out [B,Cout,2H,2W], grad_w
  * [Cin,Cout,4,4].  Three-term bf16 form, six products, fp32 accumulation; one partial [16][32][32] block per workgroup in `workspace`
@@ -429,9 +437,9 @@ int ss_conv2d_k1_f16s_pair_fwd(const float* in_a, const float* in_b, const void*
                                float* out, int B, int Cin, long long npos, int Cout, int relu, ss_stream_t stream);
 /* nn.Conv2d weight [Cout,Cin,1,1] fp32 (models/SemStereo.py:213-217) -> the fragments of ss_conv2d_k1_f16s_fwd:
  * [ceil(Cin/32)][ceil(Cout/32)][2 K-steps][2 terms][2 channel octets][32 output channels][8] fp16 of w scaled per output channel by
- * a power of two, + float[32 ceil(Cout/32)] of the inverse scales: ceil(Cin/32) * ceil(Cout/32) * 4096 + 128 * ceil(Cout/32) bytes,
- * 16-byte aligned. */
+ * a power of two, + float[32 ceil(Cout/32)] of the inverse scales (ss_pack_conv2d_k1_weights_f16s_bytes), 16-byte aligned. */
 int ss_pack_conv2d_k1_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);
+int ss_pack_conv2d_k1_weights_f16s_bytes(int Cout, int Cin, long long* bytes);
 /* The segmentation head up to its logits (segmenthead.forward, models/submodule.py:42-44: conv1 = BasicConv(Cin, 32, 3x3, padding 1)
  * = Conv2d(bias=False) + BatchNorm2d + ReLU, :89-116, then conv2 = nn.Conv2d(32, K, 1, bias=True); `head_l` / `head_r`,
  * models/SemStereo.py:200-201, 254-255) in one pass: the 32-channel map stays in the accumulators.  in [B,Cin,H,W], Cin % 8 == 0;
@@ -440,8 +448,9 @@ int ss_pack_conv2d_k1_weights_f16s(const float* w, void* wsplit, int Cout, int C
 int ss_seghead_logits_fwd(const float* in, const void* wsplit, const float* scale, const float* shift, const float* w2,
                           const float* bias, float* out, int B, int Cin, int H, int W, int K, ss_stream_t stream);
 /* conv1.conv.weight [32,Cin,3,3] fp32 -> the fragments of ss_seghead_logits_fwd: [Cin/8][5 K-steps][2 terms][2 taps][32 channels][8]
- * fp16 + float[32] inverse scales: Cin/8 * 10240 + 128 bytes, 16-byte aligned. */
+ * fp16 + float[32] inverse scales (ss_pack_seghead_weights_f16s_bytes), 16-byte aligned.  Cin % 8 == 0. */
 int ss_pack_seghead_weights_f16s(const float* w, void* wsplit, int Cin, ss_stream_t stream);
+int ss_pack_seghead_weights_f16s_bytes(int Cin, long long* bytes);
 /* F.interpolate(in, size=(2H, 2W), mode="bilinear", align_corners=False) of [B,C,H,W] -> [B,C,2H,2W] (segmenthead.forward with
  * scale_factor 2, models/submodule.py:46-51): weights 0.25 / 0.75, source index clamped at the borders, horizontal pair first. */
 int ss_bilinear_up2_fwd(const float* in, float* out, int B, int C, int H, int W, ss_stream_t stream);
@@ -460,21 +469,25 @@ int ss_seghead_tail_bwd(const float* grad_out, const float* a, const float* w2, 
                         float* workspace, int B, int K, int C, int H, int W, int up2, ss_stream_t stream);
 int ss_seghead_tail_workspace_bytes(int B, int K, int C, int H, int W, long long* bytes);
 /* two-term fp16 form of the 2-D weights (nterms = 19 of ss_conv2d_bf16s_fwd; see ss_pack_conv3d_weights_f16s):
- * ceil(Cin/8)*5*2*2*Cout*16 + 4*Cout bytes. */
+ * [ceil(Cin/8)][5][2 terms][2 halves][Cout][8] fp16 + float[Cout] (ss_pack_conv2d_weights_f16s_bytes). */
 int ss_pack_conv2d_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);
+int ss_pack_conv2d_weights_f16s_bytes(int Cout, int Cin, long long* bytes);
 /* The single-output-channel classifier heads, nn.Conv3d(C, 1, 3, padding=1, bias=False)
  * (models/SemStereo.py:228-234, classif.2 / classif_att_.2), on the split-bf16 engine with the 27 taps as
  * the matrix rows:  out [B,1,D,H,W] = relu?(scale[0] * conv(in [B,Cin,D,H,W]) + shift[0]);
- * Cin in {16, 32, 64}; nterms 6 / 3: wsplit from ss_pack_conv3d_head_weights_bf16s ((Cin/16)*3*2*32*16 bytes); nterms 19: from
- * ss_pack_conv3d_head_weights_f16s. */
+ * Cin in {16, 32, 64}; nterms 6 / 3: wsplit from ss_pack_conv3d_head_weights_bf16s ([Cin/16][3 terms][2 k-halves][32 rows][8] bf16:
+ * ss_pack_conv3d_head_weights_bf16s_bytes); nterms 19: from ss_pack_conv3d_head_weights_f16s. */
 int ss_conv3d_head_bf16s_fwd(const float* in, const void* wsplit, const float* scale, const float* shift,
                              float* out, int B, int Cin, int D, int H, int W, int relu, int nterms,
                              ss_stream_t stream);
 int ss_pack_conv3d_head_weights_bf16s(const float* w, void* wsplit, int Cin, ss_stream_t stream);
+int ss_pack_conv3d_head_weights_bf16s_bytes(int Cin, long long* bytes);
 /* nterms = 19 of the two head entry points: two fp16 terms, three products, block floating point (one power-of-two scale
  * for the weights, one per input row from a wave-wide maximum) -- half the matrix work of nterms = 6 at the same accuracy
- * class.  wsplit: (Cin/16)*2*2*32*16 bytes of terms + one float (2^-scale). */
+ * class.  wsplit: [Cin/16][2 terms][2 k-halves][32 rows][8] fp16 + one float (2^-scale) in a 16-byte tail
+ * (ss_pack_conv3d_head_weights_f16s_bytes). */
 int ss_pack_conv3d_head_weights_f16s(const float* w, void* wsplit, int Cin, ss_stream_t stream);
+int ss_pack_conv3d_head_weights_f16s_bytes(int Cin, long long* bytes);
 /* The two layers of a classifier (nn.Sequential(convbn_3d(32,32,3,1,1), ReLU, Conv3d(32,1,3,p1)), models/SemStereo.py:228-234)
  * hand their intermediate over CHANNELS-LAST, [B][D][H][W][C]: it is private to the Sequential, and with a position's
  * channels contiguous the first layer stores 16 bytes per lane and instruction and the head loads 16 (the head spends half
@@ -492,11 +505,13 @@ int ss_conv3d_head_bf16s_cl_fwd(const float* in, const void* wsplit, const float
  * contribution to the 6 x 6 x 34 output positions it touches -- a PATCH -- into `patches`
  * ([B][ceil(W/32) * ceil(H/4) * D/4][6*6*34] floats, caller-allocated scratch); a second small launch adds the <= 8 patches that
  * hold an output position, again in a fixed order: deterministic, and a pair gets the same bits at every batch size.
- *   head_w: ss_pack_classifier_head_weights(w2 [1,32,3,3,3]) -> 6144 bytes, 16-byte aligned.
+ *   head_w: ss_pack_classifier_head_weights(w2 [1,32,3,3,3]) -> [3 bf16 terms][2 K-steps][64 lanes][8]
+ *   (ss_pack_classifier_head_weights_bytes), 16-byte aligned.
  * Cin % 8 == 0, 32 intermediate channels, nterms = 19, D % 4 == 0 and a layer of at least 512 (2 x 8 x 32) tiles per pair;
  * anything else returns SS_ERR_UNSUPPORTED (the caller keeps the two-launch form above).  y is the two-launch form's y bit for
  * bit; the head's 864 products per output are summed in another order (within fp32 rounding of it). */
 int ss_pack_classifier_head_weights(const float* w2, void* out, ss_stream_t stream);
+int ss_pack_classifier_head_weights_bytes(long long* bytes);
 int ss_conv3d_classifier_fused_fwd(const float* in, const void* wsplit, const float* scale, const float* shift,
                                    const void* head_w, float* patches, float* out, int B, int Cin, int D, int H, int W,
                                    int nterms, ss_stream_t stream);
@@ -510,11 +525,12 @@ int ss_regression_topk_patched_fwd(const float* patches, const float* samples, f
  * qkv_3d and final1x1 of attention_block (models/submodule_other.py:804, 835).
  *   out [B,Cout,npos] = relu?(scale * (W in) + shift), in [B,Cin,npos], npos = D*H*W, W [Cout,Cin];
  * Cin in {32, 64, 128}; wsplit from ss_pack_pointwise_weights_bf16s
- * (ceil(Cout/32)*(Cin/16)*3*2*32*16 bytes). */
+ * ([ceil(Cout/32)][Cin/16][3 terms][2 k-halves][32 rows][8] bf16: ss_pack_pointwise_weights_bf16s_bytes). */
 int ss_conv3d_pointwise_bf16s_fwd(const float* in, const void* wsplit, const float* scale, const float* shift,
                                   float* out, int B, int Cin, int Cout, long long npos, int relu, int nterms,
                                   ss_stream_t stream);
 int ss_pack_pointwise_weights_bf16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream);
+int ss_pack_pointwise_weights_bf16s_bytes(int Cout, int Cin, long long* bytes);
 
 /* ConvTranspose3d(k3, s2, p1, output_padding 1, bias=False) [+BN] fused with the 1x1x1 skip
  * projection of hourglass.forward (models/SemStereo.py:141-142):
@@ -529,15 +545,17 @@ int ss_deconv3d_fwd(const float* in, const float* wpack, const float* scale, con
 /* The same layer on the split-bf16 engine (deconv3d_bf16s.hip): wsplit / skip_wsplit come from
  * ss_pack_deconv3d_weights_bf16s applied to the fp32 packs of ss_deconv3d_fwd (wpack [Cin][27][Cout] with the
  * BatchNorm scale folded, ntaps = 27; skip_wpack [Cs][Cout], ntaps = 1); only a common shift is applied.
- * wsplit: ceil(Cin/16)*ntaps*3*2*Cout*16 bytes. */
+ * wsplit: [ceil(Cin/16)][ntaps][3 terms][2 channel halves][Cout][8] bf16 (ss_pack_deconv3d_weights_bf16s_bytes). */
 int ss_deconv3d_bf16s_fwd(const float* in, const void* wsplit, const float* shift, const float* skip,
                           const void* skip_wsplit, float* out, int B, int Cin, int D, int H, int W, int Cout,
                           int Cs, int relu, int nterms, ss_stream_t stream);
 int ss_pack_deconv3d_weights_bf16s(const float* wpack, void* wsplit, int Cin, int Cout, int ntaps, ss_stream_t stream);
+int ss_pack_deconv3d_weights_bf16s_bytes(int Cin, int Cout, int ntaps, long long* bytes);
 /* Two-term fp16 form of the MAIN weights (ntaps = 27) for nterms = 19 of ss_deconv3d_bf16s_fwd -- the block-floating
  * scheme described at ss_pack_conv3d_weights_f16s; the skip projection keeps its bf16 pack.
- * wsplit: ceil(Cin/16)*27*2*2*Cout*16 + 4*Cout bytes. */
+ * wsplit: [ceil(Cin/16)][27][2 terms][2 channel halves][Cout][8] fp16 + float[Cout] (ss_pack_deconv3d_weights_f16s_bytes). */
 int ss_pack_deconv3d_weights_f16s(const float* wpack, void* wsplit, int Cin, int Cout, ss_stream_t stream);
+int ss_pack_deconv3d_weights_f16s_bytes(int Cin, int Cout, long long* bytes);
 /* Weight re-layout helpers (device to device): Conv3d weight [Cout,Cin,k,k,k] or
  * ConvTranspose3d weight [Cin,Cout,k,k,k] (transposed != 0) -> [Cin][k^3][Cout]. */
 int ss_pack_conv3d_weights(const float* w, float* wpack, int Cout, int Cin, int k, int transposed,

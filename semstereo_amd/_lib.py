@@ -26,7 +26,7 @@ _DECLARATION = re.compile(r"([\w \t*]+?)\s*\b(ss_\w+)\s*\(([^()]*)\)\s*;")
 _SIGNATURES = {}      # name -> argument types of every declared function (filled by load())
 EXPORTS = []          # every declared name, sorted (filled by load())
 _lib = None
-_BYTES = {}           # (query, args) -> bytes: the workspace queries are pure functions of their arguments
+_BYTES = {}           # (query, args) -> bytes: the size queries are pure functions of their arguments
 
 
 class SemStereoHipError(RuntimeError):
@@ -103,7 +103,8 @@ def call(name, *args):
 
 
 def query_bytes(name, *args):
-    """Bytes of scratch a `*_workspace_bytes` entry point asks for (no stream, no device: asked once per argument list)."""
+    """The answer of a `*_bytes` query -- a `*_workspace_bytes` scratch size or an `ss_pack_*_bytes` packed-weight size (no stream,
+    no device: asked once per argument list)."""
     if (name, args) not in _BYTES:
         n = ctypes.c_longlong(0)
         status = getattr(load(), name)(*args, ctypes.byref(n))

@@ -64,6 +64,17 @@ inline int range_halo(int dmin, int ndisp) {
 }
 __host__ __device__ inline long long ceil_div_ll(long long a, long long b) { return (a + b - 1) / b; }
 
+// A packed-weight buffer (ss_pack_*): `terms` bytes of split fragments, then -- two-term fp16 forms -- the inverse scales as floats;
+// `total` is the whole buffer, what ss_pack_*_bytes reports.  Each layout's owning .hip file has ONE function that returns this; the
+// pack entry point, the consumer's launcher and the query all take their sizes from it.
+struct Packed {
+    long long terms, total;
+};
+inline float* scales_of(void* wsplit, const Packed& p) { return reinterpret_cast<float*>(static_cast<char*>(wsplit) + p.terms); }
+inline const float* scales_of(const void* wsplit, const Packed& p) {
+    return reinterpret_cast<const float*>(static_cast<const char*>(wsplit) + p.terms);
+}
+
 // Unfused multiply / add (the reference materialises the product tensor, i.e. rounds it,
 // before reducing; keeping the two roundings makes several kernels bit-identical to it).
 // hipcc's __fmul_rn / __fadd_rn are plain `a * b` / `a + b` (clang's __clang_hip_math.h without OCML_BASIC_ROUNDED_OPERATIONS)

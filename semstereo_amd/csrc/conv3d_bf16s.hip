@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
     // group go out as one 16-byte store instead of four 4-byte ones.  Plain stride-1 form only, Cout % 8 == 0.
     constexpr bool CAN_CL = !GATED && MT == 1 && S == 1 && KD == 3;
     const bool out_cl = CAN_CL && (relu & 4) != 0;
-    // f16 form: float[Cout] of 2^-(weight scale of the channel), stored behind the packed terms
+    // f16 form: float[Cout] of 2^-(weight scale of the channel), stored behind the packed terms (must agree with conv_packed().terms)
     const float* wunscale = reinterpret_cast<const float*>(
         reinterpret_cast<const char*>(wsplit) + (size_t)((Cin + 7) / 8) * C::KSTEPS * ((NTERMS == F16X3 ? 2 : 3) * 2 * Cout * 16));
     // Output-side addressing (partial sum in, result out, gate, residual): buffer descriptors per batch element with a
@@ -894,21 +894,12 @@ __global__ void pack_weights_bf16s_kernel(const float* __restrict__ w, unsigned 
 __global__ __launch_bounds__(256) void pack_weights_f16s_fused_kernel(const float* __restrict__ w, unsigned short* __restrict__ wsplit,
                                                                        float* __restrict__ wunscale, int Cout, int Cin, int ktaps) {
     __shared__ unsigned wmax[4];
-    __shared__ float unscale_s;
     const int co = blockIdx.x, per_co = Cin * ktaps;
     const float* wc = w + (size_t)co * per_co;
     float m = 0.f;
     for (int i = threadIdx.x; i < per_co; i += 256) m = fmaxf(m, fabsf(wc[i]));
-    const unsigned wm = wave_max_bits(__float_as_uint(m));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float u = unscale_for(workgroup_exponent(wmax));
-        wunscale[co] = u;
-        unscale_s = u;
-    }
-    __syncthreads();
-    const float u = unscale_s;
+    const float u = weight_unscale(m, wmax);
+    if (threadIdx.x == 0) wunscale[co] = u;
     const int KSTEPS = (ktaps + 1) / 2, nblk = (Cin + 7) / 8;
     const int n = nblk * KSTEPS * 4 * 8;                      // this channel's slots: (blk, s, term, half, j)
     for (int e = threadIdx.x; e < n; e += 256) {
@@ -1066,42 +1057,54 @@ static int conv3d_bf16s_impl(const float* in, const void* wsplit, const float* s
 #undef SS_B
 }
 
-extern "C" int ss_pack_conv3d_weights_bf16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream) {
+// The packed weights of the 3x3x3 (ktaps 27) and 3x3 (ktaps 9) convs, the one statement of their size:
+// [ceil(Cin/8)][ceil(ktaps/2) tap pairs][3 bf16 or 2 fp16 terms][2 halves][Cout][8] two-byte terms, then (fp16 form) float[Cout].
+static ss::Packed conv_packed(int Cout, int Cin, int ktaps, bool f16) {
+    const long long terms = (long long)ss::ceil_div(Cin, 8) * ((ktaps + 1) / 2) * (f16 ? 2 : 3) * 2 * Cout * 16;
+    return {terms, terms + (f16 ? 4LL * Cout : 0)};
+}
+
+static int conv_packed_bytes(int Cout, int Cin, int ktaps, bool f16, long long* bytes) {
+    SS_REQUIRE(bytes && Cout > 0 && Cin > 0);
+    *bytes = conv_packed(Cout, Cin, ktaps, f16).total;
+    return SS_OK;
+}
+
+static int pack_conv_bf16s(const float* w, void* wsplit, int Cout, int Cin, int ktaps, ss_stream_t stream) {
     SS_REQUIRE(w && wsplit && Cout > 0 && Cin > 0);
-    const long long total = (long long)ss::ceil_div(Cin, 8) * KSTEPS * 3 * 2 * Cout * 8;
+    const long long total = conv_packed(Cout, Cin, ktaps, false).terms / 2;
     hipLaunchKernelGGL(pack_weights_bf16s_kernel, dim3((unsigned)ss::ceil_div_ll(total, 256)), dim3(256), 0,
-                       ss::as_stream(stream), w, reinterpret_cast<unsigned short*>(wsplit), Cout, Cin, 27, total);
+                       ss::as_stream(stream), w, reinterpret_cast<unsigned short*>(wsplit), Cout, Cin, ktaps, total);
     return ss::check_launch();
 }
 
 // the two-term fp16 form of the same weights (nterms = 19 of ss_conv3d_bf16s_fwd): see the top of this file
-extern "C" int ss_pack_conv3d_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream) {
+static int pack_conv_f16s(const float* w, void* wsplit, int Cout, int Cin, int ktaps, ss_stream_t stream) {
     SS_REQUIRE(w && wsplit && Cout > 0 && Cin > 0);
-    const long long total = (long long)ss::ceil_div(Cin, 8) * KSTEPS * 2 * 2 * Cout * 8;
-    float* wunscale = reinterpret_cast<float*>(reinterpret_cast<char*>(wsplit) + total * 2);
     hipLaunchKernelGGL(pack_weights_f16s_fused_kernel, dim3(Cout), dim3(256), 0, ss::as_stream(stream), w, reinterpret_cast<unsigned short*>(wsplit),
-                       wunscale, Cout, Cin, 27);
+                       ss::scales_of(wsplit, conv_packed(Cout, Cin, ktaps, true)), Cout, Cin, ktaps);
     return ss::check_launch();
 }
+
+extern "C" int ss_pack_conv3d_weights_bf16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream) {
+    return pack_conv_bf16s(w, wsplit, Cout, Cin, 27, stream);
+}
+extern "C" int ss_pack_conv3d_weights_bf16s_bytes(int Cout, int Cin, long long* bytes) { return conv_packed_bytes(Cout, Cin, 27, false, bytes); }
+extern "C" int ss_pack_conv3d_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream) {
+    return pack_conv_f16s(w, wsplit, Cout, Cin, 27, stream);
+}
+extern "C" int ss_pack_conv3d_weights_f16s_bytes(int Cout, int Cin, long long* bytes) { return conv_packed_bytes(Cout, Cin, 27, true, bytes); }
 
 // ---- the 2-D form: Conv2d(k3, s1, p1, bias=False) + affine + optional residual + ReLU on [B,C,H,W] maps (concat_feature of
 // the reference model, models/SemStereo.py:222-226): the same kernel with a depth-1 volume and 9 taps (5 K-steps) ----
 extern "C" int ss_pack_conv2d_weights_bf16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream) {
-    SS_REQUIRE(w && wsplit && Cout > 0 && Cin > 0);
-    const long long total = (long long)ss::ceil_div(Cin, 8) * 5 * 3 * 2 * Cout * 8;
-    hipLaunchKernelGGL(pack_weights_bf16s_kernel, dim3((unsigned)ss::ceil_div_ll(total, 256)), dim3(256), 0,
-                       ss::as_stream(stream), w, reinterpret_cast<unsigned short*>(wsplit), Cout, Cin, 9, total);
-    return ss::check_launch();
+    return pack_conv_bf16s(w, wsplit, Cout, Cin, 9, stream);
 }
-
+extern "C" int ss_pack_conv2d_weights_bf16s_bytes(int Cout, int Cin, long long* bytes) { return conv_packed_bytes(Cout, Cin, 9, false, bytes); }
 extern "C" int ss_pack_conv2d_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream) {
-    SS_REQUIRE(w && wsplit && Cout > 0 && Cin > 0);
-    const long long total = (long long)ss::ceil_div(Cin, 8) * 5 * 2 * 2 * Cout * 8;
-    float* wunscale = reinterpret_cast<float*>(reinterpret_cast<char*>(wsplit) + total * 2);
-    hipLaunchKernelGGL(pack_weights_f16s_fused_kernel, dim3(Cout), dim3(256), 0, ss::as_stream(stream), w, reinterpret_cast<unsigned short*>(wsplit),
-                       wunscale, Cout, Cin, 9);
-    return ss::check_launch();
+    return pack_conv_f16s(w, wsplit, Cout, Cin, 9, stream);
 }
+extern "C" int ss_pack_conv2d_weights_f16s_bytes(int Cout, int Cin, long long* bytes) { return conv_packed_bytes(Cout, Cin, 9, true, bytes); }
 
 static int conv2d_bf16s_impl(const float* in, const float* in2, int bsplit, const void* wsplit, const float* scale, const float* shift,
                             const float* residual, float* out, int B, int Cin, int H, int W, int Cout, int relu,

@@ -122,6 +122,13 @@ extern "C" int ss_pack_classifier_head_weights(const float* w2, void* out, ss_st
     return ss::check_launch();
 }
 
+// the one statement of the packed head's size: HEAD_WSLOTS 16-byte fragment slots (conv3d_bf16s.hip stages exactly these)
+extern "C" int ss_pack_classifier_head_weights_bytes(long long* bytes) {
+    SS_REQUIRE(bytes);
+    *bytes = HEAD_WSLOTS * 16;
+    return SS_OK;
+}
+
 extern "C" int ss_conv3d_classifier_fused_fwd(const float* in, const void* wsplit, const float* scale, const float* shift,
                                               const void* head_w, float* patches, float* out, int B, int Cin, int D, int H, int W,
                                               int nterms, ss_stream_t stream) {

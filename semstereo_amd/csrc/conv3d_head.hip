@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_head_bf16s(const float* __restr
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
         for (int c = 0; c < NC; ++c) a[ks][c] = __builtin_bit_cast(bf16x8, wsplit[((ks * (F16 ? 2 : 3) + c) * 2 + half) * 32 + l31]);
-    // f16 form: 2^-(weight scale), one float behind the KS * 2 * 2 * 32 fragment slots
+    // f16 form: 2^-(weight scale), one float behind the KS * 2 * 2 * 32 fragment slots (must agree with head_packed().terms)
     const float w_unscale = F16 ? *reinterpret_cast<const float*>(wsplit + KS * 2 * 2 * 32) : 1.0f;
 
     const __amdgpu_buffer_rsrc_t ires = __builtin_amdgcn_make_buffer_rsrc(
@@ -215,10 +215,7 @@ __global__ __launch_bounds__(256) void pack_head_weights_f16s_kernel(const float
     __shared__ unsigned wmax[4];
     float m = 0.f;
     for (int i = threadIdx.x; i < Cin * 27; i += 256) m = fmaxf(m, fabsf(w[i]));
-    const unsigned wm = wave_max_bits(__float_as_uint(m));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
-    __syncthreads();
-    const float unscale = unscale_for(workgroup_exponent(wmax));
+    const float unscale = weight_unscale(m, wmax);
     if (threadIdx.x == 0) *reinterpret_cast<float*>(wsplit + total) = unscale;
     for (int i = threadIdx.x; i < total; i += 256) {
         const int j = i % 8;
@@ -261,9 +258,24 @@ int launch_head_tile(const float* in, const void* wsplit, const float* scale, co
 
 }  // namespace
 
+// The packed weights of the 32 -> 1 head, the one statement of their size: [Cin/16][3 bf16 or 2 fp16 terms][2 k-halves][32 rows][8]
+// two-byte terms, then (fp16 form) one float in a 16-byte tail, so that the buffer stays a whole number of fragment slots.
+static ss::Packed head_packed(int Cin, bool f16) {
+    const long long terms = (long long)(Cin / 16) * (f16 ? 2 : 3) * 2 * 32 * 16;
+    return {terms, terms + (f16 ? 16 : 0)};
+}
+
+static int head_packed_bytes(int Cin, bool f16, long long* bytes) {
+    SS_REQUIRE(bytes && Cin > 0 && Cin % 16 == 0);
+    *bytes = head_packed(Cin, f16).total;
+    return SS_OK;
+}
+extern "C" int ss_pack_conv3d_head_weights_bf16s_bytes(int Cin, long long* bytes) { return head_packed_bytes(Cin, false, bytes); }
+extern "C" int ss_pack_conv3d_head_weights_f16s_bytes(int Cin, long long* bytes) { return head_packed_bytes(Cin, true, bytes); }
+
 extern "C" int ss_pack_conv3d_head_weights_bf16s(const float* w, void* wsplit, int Cin, ss_stream_t stream) {
     SS_REQUIRE(w && wsplit && Cin > 0 && Cin % 16 == 0);
-    const int total = (Cin / 16) * 3 * 2 * 32 * 8;
+    const int total = (int)(head_packed(Cin, false).terms / 2);
     hipLaunchKernelGGL(pack_head_weights_kernel, dim3(ss::ceil_div(total, 256)), dim3(256), 0, ss::as_stream(stream), w,
                        reinterpret_cast<unsigned short*>(wsplit), Cin, total);
     return ss::check_launch();
@@ -271,7 +283,7 @@ extern "C" int ss_pack_conv3d_head_weights_bf16s(const float* w, void* wsplit, i
 
 extern "C" int ss_pack_conv3d_head_weights_f16s(const float* w, void* wsplit, int Cin, ss_stream_t stream) {
     SS_REQUIRE(w && wsplit && Cin > 0 && Cin % 16 == 0);
-    const int total = (Cin / 16) * 2 * 2 * 32 * 8;
+    const int total = (int)(head_packed(Cin, true).terms / 2);         // (the kernel writes the scale behind them)
     hipLaunchKernelGGL(pack_head_weights_f16s_kernel, dim3(1), dim3(256), 0, ss::as_stream(stream), w,
                        reinterpret_cast<unsigned short*>(wsplit), Cin, total);
     return ss::check_launch();
@@ -436,9 +448,18 @@ int launch_pointwise(const float* in, const void* wsplit, const float* scale, co
 
 }  // namespace
 
+// the one statement of the packed 1x1x1 weights' size: [ceil(Cout/32)][Cin/16][3 terms][2 k-halves][32 rows][8] bf16
+static long long pointwise_packed_bytes(int Cout, int Cin) { return (long long)ss::ceil_div(Cout, 32) * (Cin / 16) * 3 * 2 * 32 * 16; }
+
+extern "C" int ss_pack_pointwise_weights_bf16s_bytes(int Cout, int Cin, long long* bytes) {
+    SS_REQUIRE(bytes && Cout > 0 && Cin > 0 && Cin % 16 == 0);
+    *bytes = pointwise_packed_bytes(Cout, Cin);
+    return SS_OK;
+}
+
 extern "C" int ss_pack_pointwise_weights_bf16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream) {
     SS_REQUIRE(w && wsplit && Cout > 0 && Cin > 0 && Cin % 16 == 0);
-    const int total = ss::ceil_div(Cout, 32) * (Cin / 16) * 3 * 2 * 32 * 8;
+    const int total = (int)(pointwise_packed_bytes(Cout, Cin) / 2);
     hipLaunchKernelGGL(pack_pointwise_weights_kernel, dim3(ss::ceil_div(total, 256)), dim3(256), 0, ss::as_stream(stream), w,
                        reinterpret_cast<unsigned short*>(wsplit), Cout, Cin, total);
     return ss::check_launch();

@@ -49,6 +49,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_pre(const uint4* __restrict__ x
     };
     const bool res_pre = (relu & 2) != 0 && residual != nullptr;      // `residual`: a partial sum of the same convolution
     const int nchunks = Cin / 8;
+    // (must agree with conv_packed().terms of conv3d_bf16s.hip, whose ss_pack_conv3d_weights_f16s made wsplit)
     const float* wunscale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wsplit) + (size_t)nchunks * P_KSTEPS * (2 * 2 * Cout * 16));
     const size_t plane = (size_t)H * W;
     const unsigned ochan_b = (unsigned)((size_t)D * plane * 4), gchan_b = (unsigned)(plane * 4);

@@ -176,22 +176,13 @@ __global__ __launch_bounds__(256, 2) void deconv2d_f16s(const float* __restrict_
 __global__ __launch_bounds__(256) void pack_deconv2d_f16s_kernel(const float* __restrict__ w, unsigned short* __restrict__ wsplit,
                                                                   float* __restrict__ wunscale, int Cin, int Cout) {
     __shared__ unsigned wmax[4];
-    __shared__ float unscale_s;
     const int co = blockIdx.x, nct = gridDim.x / 32;
     const bool live = co < Cout;
     float m = 0.f;
     if (live)
         for (int i = threadIdx.x; i < Cin * 16; i += 256) m = fmaxf(m, fabsf(w[((size_t)(i / 16) * Cout + co) * 16 + i % 16]));
-    const unsigned wm = wave_max_bits(__float_as_uint(m));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float u = unscale_for(workgroup_exponent(wmax));
-        wunscale[co] = u;
-        unscale_s = u;
-    }
-    __syncthreads();
-    const float u = unscale_s;
+    const float u = weight_unscale(m, wmax);
+    if (threadIdx.x == 0) wunscale[co] = u;
     const int nchunks = (Cin + 7) / 8, ct = co / 32, cl = co % 32;
     const int n = nchunks * 32 * 8;                            // this channel's elements: (chunk, class, dy, term, dx, j)
     for (int e = threadIdx.x; e < n; e += 256) {
@@ -210,6 +201,12 @@ __global__ __launch_bounds__(256) void pack_deconv2d_f16s_kernel(const float* __
     }
 }
 
+// the one statement of that layout's size: DCfg::WSL 16-byte slots per (chunk, channel tile), then float[32 ceil(Cout/32)]
+ss::Packed deconv2d_packed(int Cin, int Cout) {
+    const long long nct = ss::ceil_div(Cout, 32), terms = ss::ceil_div(Cin, 8) * nct * DCfg<1>::WSL * 16;
+    return {terms, terms + 4 * 32 * nct};
+}
+
 template <int NT>
 int launch_deconv2d(const float* in, const float* in2, int bsplit, const void* wsplit, const float* scale, const float* shift, float* out,
                     int B, int Cin, int H, int W, int Cout, int relu, hipStream_t st) {
@@ -217,9 +214,9 @@ int launch_deconv2d(const float* in, const float* in2, int bsplit, const void* w
     const int tiles_w = ss::ceil_div(W, 32), nct = ss::ceil_div(Cout, 32);
     const long long tiles = (long long)tiles_w * ss::ceil_div(H, C::TH);
     if (tiles > 0x7fffffffLL || nct > 65535 || B > 65535) return SS_ERR_UNSUPPORTED;
-    const float* wunscale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wsplit) + (size_t)ss::ceil_div(Cin, 8) * nct * C::WSL * 16);
     hipLaunchKernelGGL(deconv2d_f16s<NT>, dim3((unsigned)tiles, nct, B), dim3(256), 0, st, in, in2, bsplit,
-                       reinterpret_cast<const uint4*>(wsplit), wunscale, scale, shift, out, Cin, H, W, Cout, tiles_w, relu ? 1 : 0);
+                       reinterpret_cast<const uint4*>(wsplit), ss::scales_of(wsplit, deconv2d_packed(Cin, Cout)), scale, shift, out, Cin, H, W,
+                       Cout, tiles_w, relu ? 1 : 0);
     return ss::check_launch();
 }
 
@@ -255,10 +252,13 @@ extern "C" int ss_deconv2d_bf16s_pair_fwd(const float* in_a, const float* in_b, 
 extern "C" int ss_pack_deconv2d_weights_f16s(const float* w, void* wsplit, int Cin, int Cout, ss_stream_t stream) {
     SS_REQUIRE(w && wsplit && Cout > 0 && Cin > 0);
     SS_REQUIRE((reinterpret_cast<uintptr_t>(wsplit) & 15) == 0);
-    const int nct = ss::ceil_div(Cout, 32);
-    const size_t terms = (size_t)ss::ceil_div(Cin, 8) * nct * 16 * 64 * 8;
-    float* wunscale = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(wsplit) + terms);
-    hipLaunchKernelGGL(pack_deconv2d_f16s_kernel, dim3(nct * 32), dim3(256), 0, ss::as_stream(stream), w,
-                       reinterpret_cast<unsigned short*>(wsplit), wunscale, Cin, Cout);
+    hipLaunchKernelGGL(pack_deconv2d_f16s_kernel, dim3(ss::ceil_div(Cout, 32) * 32), dim3(256), 0, ss::as_stream(stream), w,
+                       reinterpret_cast<unsigned short*>(wsplit), ss::scales_of(wsplit, deconv2d_packed(Cin, Cout)), Cin, Cout);
     return ss::check_launch();
+}
+
+extern "C" int ss_pack_deconv2d_weights_f16s_bytes(int Cin, int Cout, long long* bytes) {
+    SS_REQUIRE(bytes && Cout > 0 && Cin > 0);
+    *bytes = deconv2d_packed(Cin, Cout).total;
+    return SS_OK;
 }

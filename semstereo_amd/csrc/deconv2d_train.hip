@@ -169,22 +169,13 @@ __global__ __launch_bounds__(256, 2) void conv2d_k4s2_f16s(const float* __restri
 __global__ __launch_bounds__(256) void pack_conv2d_k4s2_f16s_kernel(const float* __restrict__ w, unsigned short* __restrict__ wsplit,
                                                                      float* __restrict__ wunscale, int Cout, int Cin) {
     __shared__ unsigned wmax[4];
-    __shared__ float unscale_s;
     const int co = blockIdx.x, nct = gridDim.x / 32;
     const bool live = co < Cout;
     float m = 0.f;
     if (live)
         for (int i = threadIdx.x; i < Cin * 16; i += 256) m = fmaxf(m, fabsf(w[(size_t)co * Cin * 16 + i]));
-    const unsigned wm = wave_max_bits(__float_as_uint(m));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float u = unscale_for(workgroup_exponent(wmax));
-        wunscale[co] = u;
-        unscale_s = u;
-    }
-    __syncthreads();
-    const float u = unscale_s;
+    const float u = weight_unscale(m, wmax);
+    if (threadIdx.x == 0) wunscale[co] = u;
     const int nchunks = (Cin + 7) / 8, ct = co / 32, cl = co % 32;
     const int n = nchunks * 32 * 8;                            // this channel's elements: (chunk, step, term, half, j)
     for (int e = threadIdx.x; e < n; e += 256) {
@@ -202,15 +193,20 @@ __global__ __launch_bounds__(256) void pack_conv2d_k4s2_f16s_kernel(const float*
     }
 }
 
+// the one statement of that layout's size: GCfg::WSL 16-byte slots per (chunk, channel tile), then float[32 ceil(Cout/32)]
+ss::Packed conv2d_k4s2_packed(int Cout, int Cin) {
+    const long long nct = ss::ceil_div(Cout, 32), terms = ss::ceil_div(Cin, 8) * nct * GCfg<1>::WSL * 16;
+    return {terms, terms + 4 * 32 * nct};
+}
+
 template <int NT>
 int launch_conv2d_k4s2(const float* in, const void* wsplit, float* out, int B, int Cin, int H, int W, int Cout, hipStream_t st) {
     using C = GCfg<NT>;
     const int tiles_w = ss::ceil_div(W / 2, 32), nct = ss::ceil_div(Cout, 32);
     const long long tiles = (long long)tiles_w * ss::ceil_div(H / 2, C::TH);
     if (tiles > 0x7fffffffLL || nct > 65535 || B > 65535) return SS_ERR_UNSUPPORTED;
-    const float* wunscale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wsplit) + (size_t)ss::ceil_div(Cin, 8) * nct * C::WSL * 16);
     hipLaunchKernelGGL(conv2d_k4s2_f16s<NT>, dim3((unsigned)tiles, nct, B), dim3(256), 0, st, in, reinterpret_cast<const uint4*>(wsplit),
-                       wunscale, out, Cin, H, W, Cout, tiles_w);
+                       ss::scales_of(wsplit, conv2d_k4s2_packed(Cout, Cin)), out, Cin, H, W, Cout, tiles_w);
     return ss::check_launch();
 }
 
@@ -369,12 +365,15 @@ extern "C" int ss_conv2d_k4s2_f16s_fwd(const float* in, const void* wsplit, floa
 extern "C" int ss_pack_conv2d_k4s2_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream) {
     SS_REQUIRE(w && wsplit && Cout > 0 && Cin > 0);
     SS_REQUIRE((reinterpret_cast<uintptr_t>(wsplit) & 15) == 0);
-    const int nct = ss::ceil_div(Cout, 32);
-    const size_t terms = (size_t)ss::ceil_div(Cin, 8) * nct * 16 * 64 * 8;
-    float* wunscale = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(wsplit) + terms);
-    hipLaunchKernelGGL(pack_conv2d_k4s2_f16s_kernel, dim3(nct * 32), dim3(256), 0, ss::as_stream(stream), w,
-                       reinterpret_cast<unsigned short*>(wsplit), wunscale, Cout, Cin);
+    hipLaunchKernelGGL(pack_conv2d_k4s2_f16s_kernel, dim3(ss::ceil_div(Cout, 32) * 32), dim3(256), 0, ss::as_stream(stream), w,
+                       reinterpret_cast<unsigned short*>(wsplit), ss::scales_of(wsplit, conv2d_k4s2_packed(Cout, Cin)), Cout, Cin);
     return ss::check_launch();
+}
+
+extern "C" int ss_pack_conv2d_k4s2_weights_f16s_bytes(int Cout, int Cin, long long* bytes) {
+    SS_REQUIRE(bytes && Cout > 0 && Cin > 0);
+    *bytes = conv2d_k4s2_packed(Cout, Cin).total;
+    return SS_OK;
 }
 
 extern "C" int ss_deconv2d_k4s2_wgrad_workspace_bytes(int B, int Cin, int H, int W, int Cout, long long* bytes) {

@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
     const int wlane = (half * Cout + min(co0 + l31, Cout - 1)) * 16;
     const int wstep = NCW * 2 * Cout * 16;                     // bytes per K-step of the main weights
     const int swstep = 3 * 2 * Cout * 16;                      // ... of the skip projection's (always three bf16 terms)
-    const float* wunscale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wsplit) + (size_t)G * wstep);
+    const float* wunscale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wsplit) + (size_t)G * wstep);   // (must agree with deconv_packed().terms)
     const __amdgpu_buffer_rsrc_t wres = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint4*>(wsplit), 0, (int)min((long long)G * wstep, 0x7fffffffLL), 0x00020000);
     const __amdgpu_buffer_rsrc_t ires = __builtin_amdgcn_make_buffer_rsrc(
@@ -579,10 +579,8 @@ __global__ __launch_bounds__(256) void deconv_weight_unscale_f16s_kernel(const f
     __shared__ unsigned wmax[4];
     float m = 0.f;
     for (int i = threadIdx.x; i < rows; i += 256) m = fmaxf(m, fabsf(wpack[(size_t)i * Cout + blockIdx.x]));
-    const unsigned wm = wave_max_bits(__float_as_uint(m));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
-    __syncthreads();
-    if (threadIdx.x == 0) wunscale[blockIdx.x] = unscale_for(workgroup_exponent(wmax));
+    const float u = weight_unscale(m, wmax);
+    if (threadIdx.x == 0) wunscale[blockIdx.x] = u;
 }
 // pass 2: -> [ceil(Cin/16)][27 K-steps][2 terms][2 channel halves][Cout][8] fp16 of w / wunscale[co]
 __global__ void pack_deconv_weights_f16s_kernel(const float* __restrict__ wpack, unsigned short* __restrict__ wsplit,
@@ -652,9 +650,28 @@ int launch_db_all(const float* in, const void* wsplit, const float* shift, const
 
 }  // namespace
 
+// The packed weights of the transposed conv (ntaps 27) and of its skip projection (ntaps 1), the one statement of their size:
+// [ceil(Cin/16)][ntaps][3 bf16 or 2 fp16 terms][2 channel halves][Cout][8] two-byte terms, then (fp16 form) float[Cout].
+static ss::Packed deconv_packed(int Cin, int Cout, int ntaps, bool f16) {
+    const long long terms = (long long)ss::ceil_div(Cin, 16) * ntaps * (f16 ? 2 : 3) * 2 * Cout * 16;
+    return {terms, terms + (f16 ? 4LL * Cout : 0)};
+}
+
+extern "C" int ss_pack_deconv3d_weights_bf16s_bytes(int Cin, int Cout, int ntaps, long long* bytes) {
+    SS_REQUIRE(bytes && Cin > 0 && Cout > 0 && (ntaps == 27 || ntaps == 1));
+    *bytes = deconv_packed(Cin, Cout, ntaps, false).total;
+    return SS_OK;
+}
+
+extern "C" int ss_pack_deconv3d_weights_f16s_bytes(int Cin, int Cout, long long* bytes) {
+    SS_REQUIRE(bytes && Cin > 0 && Cout > 0);
+    *bytes = deconv_packed(Cin, Cout, 27, true).total;
+    return SS_OK;
+}
+
 extern "C" int ss_pack_deconv3d_weights_bf16s(const float* wpack, void* wsplit, int Cin, int Cout, int ntaps, ss_stream_t stream) {
     SS_REQUIRE(wpack && wsplit && Cin > 0 && Cout > 0 && (ntaps == 27 || ntaps == 1));
-    const long long total = (long long)((Cin + 15) / 16) * ntaps * 3 * 2 * Cout * 8;
+    const long long total = deconv_packed(Cin, Cout, ntaps, false).terms / 2;
     hipLaunchKernelGGL(pack_deconv_weights_kernel, dim3((unsigned)ss::ceil_div_ll(total, 256)), dim3(256), 0, ss::as_stream(stream),
                        wpack, reinterpret_cast<unsigned short*>(wsplit), Cin, Cout, ntaps, total);
     return ss::check_launch();
@@ -663,8 +680,9 @@ extern "C" int ss_pack_deconv3d_weights_bf16s(const float* wpack, void* wsplit, 
 // the two-term fp16 form of the main weights (nterms = 19 of ss_deconv3d_bf16s_fwd; the skip projection keeps the bf16 form)
 extern "C" int ss_pack_deconv3d_weights_f16s(const float* wpack, void* wsplit, int Cin, int Cout, ss_stream_t stream) {
     SS_REQUIRE(wpack && wsplit && Cin > 0 && Cout > 0);
-    const long long total = (long long)((Cin + 15) / 16) * 27 * 2 * 2 * Cout * 8;
-    float* wunscale = reinterpret_cast<float*>(reinterpret_cast<char*>(wsplit) + total * 2);
+    const ss::Packed p = deconv_packed(Cin, Cout, 27, true);
+    const long long total = p.terms / 2;
+    float* wunscale = ss::scales_of(wsplit, p);
     hipLaunchKernelGGL(deconv_weight_unscale_f16s_kernel, dim3(Cout), dim3(256), 0, ss::as_stream(stream), wpack, wunscale, Cout, Cin * 27);
     hipLaunchKernelGGL(pack_deconv_weights_f16s_kernel, dim3((unsigned)ss::ceil_div_ll(total, 256)), dim3(256), 0, ss::as_stream(stream),
                        wpack, reinterpret_cast<unsigned short*>(wsplit), wunscale, Cin, Cout, total);

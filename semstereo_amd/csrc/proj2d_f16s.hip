@@ -162,22 +162,13 @@ __global__ __launch_bounds__(256, 2) void proj2d_f16s(const float* __restrict__ 
 __global__ __launch_bounds__(256) void pack_proj2d_f16s_kernel(const float* __restrict__ w, unsigned short* __restrict__ wsplit,
                                                                 float* __restrict__ wunscale, int Cout, int Cin) {
     __shared__ unsigned wmax[4];
-    __shared__ float unscale_s;
     const int co = blockIdx.x, nmt = gridDim.x / 32;
     const bool live = co < Cout;
     float m = 0.f;
     if (live)
         for (int i = threadIdx.x; i < Cin; i += 256) m = fmaxf(m, fabsf(w[(size_t)co * Cin + i]));
-    const unsigned wm = wave_max_bits(__float_as_uint(m));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float u = unscale_for(workgroup_exponent(wmax));
-        wunscale[co] = u;
-        unscale_s = u;
-    }
-    __syncthreads();
-    const float u = unscale_s;
+    const float u = weight_unscale(m, wmax);
+    if (threadIdx.x == 0) wunscale[co] = u;
     const int nchunks = (Cin + P_CHUNK - 1) / P_CHUNK, t = co / 32, cl = co % 32;
     const int n = nchunks * 2 * 2 * 2 * 8;                     // this channel's elements: (chunk, K-step, term, octet, j)
     for (int e = threadIdx.x; e < n; e += 256) {
@@ -195,16 +186,21 @@ __global__ __launch_bounds__(256) void pack_proj2d_f16s_kernel(const float* __re
     }
 }
 
+// the one statement of that layout's size: 256 16-byte slots per (chunk, channel tile), then float[32 ceil(Cout/32)]
+ss::Packed proj2d_packed(int Cout, int Cin) {
+    const long long nmt = ss::ceil_div(Cout, 32), terms = ss::ceil_div(Cin, P_CHUNK) * nmt * 256 * 16;
+    return {terms, terms + 4 * 32 * nmt};
+}
+
 template <int MT>
 int launch_proj2d(const float* in, const float* in2, int bsplit, const void* wsplit, const float* scale, const float* shift, float* out,
                   int B, int Cin, long long npos, int Cout, int relu, hipStream_t st) {
     const int nmt = ss::ceil_div(Cout, 32), groups = ss::ceil_div(nmt, 4 * MT);
     const long long tiles = ss::ceil_div_ll(npos, P_TILE);
     if (tiles > 0x7fffffffLL || groups > 65535 || B > 65535) return SS_ERR_UNSUPPORTED;
-    const float* wunscale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wsplit) +
-                                                           (size_t)ss::ceil_div(Cin, P_CHUNK) * nmt * 256 * 16);
     hipLaunchKernelGGL(proj2d_f16s<MT>, dim3((unsigned)tiles, groups, B), dim3(256), 0, st, in, in2, bsplit,
-                       reinterpret_cast<const uint4*>(wsplit), wunscale, scale, shift, out, Cin, (int)npos, Cout, nmt, relu ? 1 : 0);
+                       reinterpret_cast<const uint4*>(wsplit), ss::scales_of(wsplit, proj2d_packed(Cout, Cin)), scale, shift, out, Cin,
+                       (int)npos, Cout, nmt, relu ? 1 : 0);
     return ss::check_launch();
 }
 
@@ -244,10 +240,13 @@ extern "C" int ss_conv2d_k1_f16s_pair_fwd(const float* in_a, const float* in_b, 
 extern "C" int ss_pack_conv2d_k1_weights_f16s(const float* w, void* wsplit, int Cout, int Cin, ss_stream_t stream) {
     SS_REQUIRE(w && wsplit && Cout > 0 && Cin > 0);
     SS_REQUIRE((reinterpret_cast<uintptr_t>(wsplit) & 15) == 0);
-    const int nmt = ss::ceil_div(Cout, 32);
-    const size_t terms = (size_t)ss::ceil_div(Cin, P_CHUNK) * nmt * 256 * 8;
-    float* wunscale = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(wsplit) + terms);
-    hipLaunchKernelGGL(pack_proj2d_f16s_kernel, dim3(nmt * 32), dim3(256), 0, ss::as_stream(stream), w,
-                       reinterpret_cast<unsigned short*>(wsplit), wunscale, Cout, Cin);
+    hipLaunchKernelGGL(pack_proj2d_f16s_kernel, dim3(ss::ceil_div(Cout, 32) * 32), dim3(256), 0, ss::as_stream(stream), w,
+                       reinterpret_cast<unsigned short*>(wsplit), ss::scales_of(wsplit, proj2d_packed(Cout, Cin)), Cout, Cin);
     return ss::check_launch();
+}
+
+extern "C" int ss_pack_conv2d_k1_weights_f16s_bytes(int Cout, int Cin, long long* bytes) {
+    SS_REQUIRE(bytes && Cout > 0 && Cin > 0);
+    *bytes = proj2d_packed(Cout, Cin).total;
+    return SS_OK;
 }

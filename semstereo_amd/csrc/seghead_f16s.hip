@@ -180,20 +180,11 @@ __global__ __launch_bounds__(256, 2) void seghead_logits_f16s(const float* __res
 __global__ __launch_bounds__(256) void pack_seghead_f16s_kernel(const float* __restrict__ w, unsigned short* __restrict__ wsplit,
                                                                  float* __restrict__ wunscale, int Cin) {
     __shared__ unsigned wmax[4];
-    __shared__ float unscale_s;
     const int co = blockIdx.x;
     float m = 0.f;
     for (int i = threadIdx.x; i < Cin * 9; i += 256) m = fmaxf(m, fabsf(w[(size_t)co * Cin * 9 + i]));
-    const unsigned wm = wave_max_bits(__float_as_uint(m));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float u = unscale_for(workgroup_exponent(wmax));
-        wunscale[co] = u;
-        unscale_s = u;
-    }
-    __syncthreads();
-    const float u = unscale_s;
+    const float u = weight_unscale(m, wmax);
+    if (threadIdx.x == 0) wunscale[co] = u;
     const int n = (Cin / 8) * 5 * 2 * 2 * 8;                   // this channel's elements: (chunk, K-step, term, tap half, j)
     for (int e = threadIdx.x; e < n; e += 256) {
         const int j = e % 8;
@@ -260,14 +251,24 @@ __global__ __launch_bounds__(256) void bilinear_up2_kernel(const float* __restri
 
 }  // namespace
 
+// the one statement of the packed conv1 weights' size: H_WSL 16-byte slots per chunk of 8 input channels, then float[32]
+static ss::Packed seghead_packed(int Cin) {
+    const long long terms = (long long)(Cin / 8) * H_WSL * 16;
+    return {terms, terms + 4 * 32};
+}
+
 extern "C" int ss_pack_seghead_weights_f16s(const float* w, void* wsplit, int Cin, ss_stream_t stream) {
     SS_REQUIRE(w && wsplit && Cin > 0 && Cin % 8 == 0);
     SS_REQUIRE((reinterpret_cast<uintptr_t>(wsplit) & 15) == 0);
-    const size_t terms = (size_t)(Cin / 8) * H_WSL * 8;
-    float* wunscale = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(wsplit) + terms);
     hipLaunchKernelGGL(pack_seghead_f16s_kernel, dim3(32), dim3(256), 0, ss::as_stream(stream), w,
-                       reinterpret_cast<unsigned short*>(wsplit), wunscale, Cin);
+                       reinterpret_cast<unsigned short*>(wsplit), ss::scales_of(wsplit, seghead_packed(Cin)), Cin);
     return ss::check_launch();
+}
+
+extern "C" int ss_pack_seghead_weights_f16s_bytes(int Cin, long long* bytes) {
+    SS_REQUIRE(bytes && Cin > 0 && Cin % 8 == 0);
+    *bytes = seghead_packed(Cin).total;
+    return SS_OK;
 }
 
 extern "C" int ss_seghead_logits_fwd(const float* in, const void* wsplit, const float* scale, const float* shift, const float* w2,
@@ -281,9 +282,9 @@ extern "C" int ss_seghead_logits_fwd(const float* in, const void* wsplit, const 
     const int tiles_w = ss::ceil_div(W, 32);
     const long long tiles = (long long)tiles_w * ss::ceil_div(H, H_TH);
     if (tiles > 0x7fffffffLL || B > 65535) return SS_ERR_UNSUPPORTED;
-    const float* wunscale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wsplit) + (size_t)(Cin / 8) * H_WSL * 16);
     hipLaunchKernelGGL(seghead_logits_f16s, dim3((unsigned)tiles, B), dim3(256), 0, ss::as_stream(stream), in,
-                       reinterpret_cast<const uint4*>(wsplit), wunscale, scale, shift, w2, bias, out, Cin, H, W, K, tiles_w);
+                       reinterpret_cast<const uint4*>(wsplit), ss::scales_of(wsplit, seghead_packed(Cin)), scale, shift, w2, bias, out, Cin, H,
+                       W, K, tiles_w);
     return ss::check_launch();
 }
 

@@ -107,8 +107,18 @@ struct BlockExp {
     __device__ __forceinline__ float acc_unscale() const { return unscale_for(e_cur); }   // ... and back, in the epilogue
 };
 
-// Packed weights: a channel's values are divided by u = unscale_for(workgroup_exponent(...)), which brings its max |w| into
-// [2^14, 2^15); term 0 / 1 of x = w / u as an fp16 bit pattern
+// Packed weights: a channel's values are divided by u, the power of two that brings the channel's max |w| into [2^14, 2^15).
+// weight_unscale: `m` = this thread's max |w| over its share of the channel, `wmax` = the workgroup's LDS array -> u, the same
+// value in every thread.  Synchronisation: called by ALL 256 threads of the workgroup, outside divergent code; it holds one
+// __syncthreads() (between the four waves' writes of `wmax` and everybody's read).  `wmax` is not read before that barrier and
+// not written after it, so a kernel that calls this once needs no barrier of its own; a second call needs one in between.
+__device__ __forceinline__ float weight_unscale(float m, unsigned (&wmax)[4]) {
+    const unsigned wm = wave_max_bits(__float_as_uint(m));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
+    __syncthreads();
+    return unscale_for(workgroup_exponent(wmax));
+}
+// term 0 / 1 of x = w / u as an fp16 bit pattern
 __device__ __forceinline__ unsigned short split_weight_f16(float x, int term) {
     const _Float16 h = (_Float16)x;
     const _Float16 l = (_Float16)(x - (float)h);

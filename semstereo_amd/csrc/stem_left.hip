@@ -515,9 +515,12 @@ __global__ __launch_bounds__(256) void pack_stem_left_f16s_kernel(const float* _
     }
 }
 
+// the one statement of that layout's size (C = Cout = 32): the fp16 terms, then 12 floats per (channel group, shift, lane half)
+ss::Packed stem_left_packed() { return {2LL * WFRAG_HALVES, 2LL * WFRAG_HALVES + 4 * NCG * 9 * 2 * 12}; }
+
 template <int ND>
 int launch_mfma(const float* left, const void* wsplit, const float* att, float* out, int B, int H, int W, hipStream_t st) {
-    const float4* winv = reinterpret_cast<const float4*>(reinterpret_cast<const unsigned short*>(wsplit) + WFRAG_HALVES);
+    const float4* winv = reinterpret_cast<const float4*>(ss::scales_of(wsplit, stem_left_packed()));
     dim3 grid(ss::ceil_div(W, FTW), ss::ceil_div(H, FTH), B);
     hipLaunchKernelGGL(stem_left_mfma<ND>, grid, dim3(256), 0, st, left, reinterpret_cast<const uint4*>(wsplit), winv, att, out, H, W);
     return ss::check_launch();
@@ -543,8 +546,14 @@ extern "C" int ss_pack_stem_left_weights_f16s(const float* w, void* wsplit, int 
     SS_REQUIRE(w && wsplit);
     SS_REQUIRE((reinterpret_cast<uintptr_t>(wsplit) & 15) == 0);
     if (C != 32 || Cout != 32) return SS_ERR_UNSUPPORTED;
-    unsigned short* ws = reinterpret_cast<unsigned short*>(wsplit);
-    hipLaunchKernelGGL(pack_stem_left_f16s_kernel, dim3(ss::ceil_div(NCG * 9 * 32, 256)), dim3(256), 0, ss::as_stream(stream), w, ws,
-                       reinterpret_cast<float*>(ws + WFRAG_HALVES));
+    hipLaunchKernelGGL(pack_stem_left_f16s_kernel, dim3(ss::ceil_div(NCG * 9 * 32, 256)), dim3(256), 0, ss::as_stream(stream), w,
+                       reinterpret_cast<unsigned short*>(wsplit), ss::scales_of(wsplit, stem_left_packed()));
     return ss::check_launch();
+}
+
+extern "C" int ss_pack_stem_left_weights_f16s_bytes(int Cout, int C, long long* bytes) {
+    SS_REQUIRE(bytes && Cout > 0 && C > 0);
+    if (C != 32 || Cout != 32) return SS_ERR_UNSUPPORTED;
+    *bytes = stem_left_packed().total;
+    return SS_OK;
 }

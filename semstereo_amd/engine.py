@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from ._host import PATH_COUNTS  # (the one dictionary: `engine.PATH_COUNTS` and `modules.PATH_COUNTS` are this object)
+from ._host import PATH_COUNTS, _c  # (the one dictionary: `engine.PATH_COUNTS` and `modules.PATH_COUNTS` are this object)
 from ._lib import call, ptr
 
 
@@ -172,10 +172,21 @@ def pack_conv_weight(w, transposed=False):
     return out
 
 
+def _pack(entry, w, *dims):
+    """fp32 weights `w` -> the int16 tensor (16-B aligned) of split fragments that the `ss_pack_*` entry point `entry` writes for the
+    scalar arguments `dims`.  Its length is the library's own statement of the layout's size (`entry`_bytes)."""
+    w = _c(w.detach().float())
+    _lib.require_device(w)
+    out = torch.empty(_lib.query_bytes(entry + "_bytes", *dims) // 2, dtype=torch.int16, device=w.device)
+    with torch.cuda.device(w.device):
+        call(entry, ptr(w), ptr(out), *dims)
+    return out
+
+
 def conv3d_hip(x, wpack, scale, shift, k, stride, relu, residual=None, gate=None):
     """Conv3d(bias=False, pad=k//2) + per-channel affine + optional residual + optional ReLU + optional
     channelAtt gate (sigmoid(gate[b,co,h,w]) broadcast over D)."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x, wpack, scale, shift, residual, gate)
     B, Cin, D, H, W = x.shape
     assert wpack.shape[0] == Cin and wpack.shape[1] == k ** 3
@@ -196,14 +207,14 @@ def conv3d_hip(x, wpack, scale, shift, k, stride, relu, residual=None, gate=None
 def deconv3d_hip(x, wpack, shift, relu, skip=None, skip_wpack=None):
     """ConvTranspose3d(k3,s2,p1,op1) [+ 1x1x1 projection of `skip`] + shift + optional ReLU.
     Per-branch BN scales are expected to be folded into the packed weights already."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x, wpack, shift, skip, skip_wpack)
     B, Cin, D, H, W = x.shape
     Cout = wpack.shape[2]
     out = torch.empty((B, Cout, 2 * D, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
     Cs = 0
     if skip is not None:
-        skip = skip if skip.is_contiguous() else skip.contiguous()
+        skip = _c(skip)
         Cs = skip.shape[1]
         assert skip.shape == (B, Cs, 2 * D, 2 * H, 2 * W) and skip_wpack.shape == (Cs, Cout)
     with torch.cuda.device(dev):
@@ -216,30 +227,23 @@ def pack_deconv_weight_bf16s(wpack, nterms=6):
     """fp32 pack [Cin][ntaps][Cout] (ntaps 27: transposed conv, BN scale folded; or [Cs][Cout]: the skip projection)
     -> split fragments for ss_deconv3d_bf16s_fwd: three bf16 terms, or (nterms 19, main weights only) two scaled fp16
     terms + the per-channel inverse scales."""
-    wpack = wpack.detach().float().contiguous()
-    _lib.require_device(wpack)
     Cin, Cout = wpack.shape[0], wpack.shape[-1]
     ntaps = 1 if wpack.dim() == 2 else wpack.shape[1]
-    with torch.cuda.device(wpack.device):
-        if nterms == 19:
-            assert ntaps == 27
-            out = torch.empty(((Cin + 15) // 16) * 27 * 2 * 2 * Cout * 8 + 2 * Cout, dtype=torch.int16, device=wpack.device)
-            call("ss_pack_deconv3d_weights_f16s", ptr(wpack), ptr(out), Cin, Cout)
-        else:
-            out = torch.empty(((Cin + 15) // 16) * ntaps * 3 * 2 * Cout * 8, dtype=torch.int16, device=wpack.device)
-            call("ss_pack_deconv3d_weights_bf16s", ptr(wpack), ptr(out), Cin, Cout, ntaps)
-    return out
+    if nterms == 19:
+        assert ntaps == 27
+        return _pack("ss_pack_deconv3d_weights_f16s", wpack, Cin, Cout)
+    return _pack("ss_pack_deconv3d_weights_bf16s", wpack, Cin, Cout, ntaps)
 
 
 def deconv3d_bf16s_hip(x, wsplit, Cout, shift, relu, nterms, skip=None, skip_wsplit=None):
     """deconv3d_hip on the split-bf16 engine."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x, shift, skip)
     B, Cin, D, H, W = x.shape
     out = torch.empty((B, Cout, 2 * D, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
     Cs = 0
     if skip is not None:
-        skip = skip if skip.is_contiguous() else skip.contiguous()
+        skip = _c(skip)
         Cs = skip.shape[1]
         assert skip.shape == (B, Cs, 2 * D, 2 * H, 2 * W)
     with torch.cuda.device(dev):
@@ -285,24 +289,15 @@ DECONV_BF16S = os.environ.get("SS_DECONV_BF16S", "1") != "0"     # transposed co
 def pack_conv_weight_bf16s(w, nterms=6):
     """[Cout,Cin,3,3,3] fp32 -> split fragments for ss_conv3d_bf16s_fwd (int16 tensor, 16-B aligned): three bf16 terms
     (nterms 6 / 3) or two scaled fp16 terms + the per-channel inverse scales (nterms 19)."""
-    w = w.detach().float().contiguous()
-    _lib.require_device(w)
     Cout, Cin = w.shape[0], w.shape[1]
     assert tuple(w.shape[2:]) == (3, 3, 3)
-    with torch.cuda.device(w.device):
-        if nterms == 19:
-            out = torch.empty(((Cin + 7) // 8) * 14 * 2 * 2 * Cout * 8 + 2 * Cout, dtype=torch.int16, device=w.device)
-            call("ss_pack_conv3d_weights_f16s", ptr(w), ptr(out), Cout, Cin)
-        else:
-            out = torch.empty(((Cin + 7) // 8) * 14 * 3 * 2 * Cout * 8, dtype=torch.int16, device=w.device)
-            call("ss_pack_conv3d_weights_bf16s", ptr(w), ptr(out), Cout, Cin)
-    return out
+    return _pack("ss_pack_conv3d_weights_f16s" if nterms == 19 else "ss_pack_conv3d_weights_bf16s", w, Cout, Cin)
 
 
 def conv3d_bf16s_hip(x, wsplit, Cout, scale, shift, relu, nterms, residual=None, gate=None, partial=None, stride=1):
     """3x3x3 Conv3d (stride 1 or 2) + affine + optional residual / ReLU on the split-bf16 engine.  `partial`
     [B,Cout,D,H,W]: a partial sum of the same convolution (other input channels), added BEFORE the affine."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x, scale, shift, residual, gate, partial)
     B, Cin, D, H, W = x.shape
     Do, Ho, Wo = [(n - 1) // stride + 1 for n in (D, H, W)]
@@ -323,7 +318,7 @@ def conv3d_bf16s_hip(x, wsplit, Cout, scale, shift, relu, nterms, residual=None,
 def classifier_cl_hip(x, ws0, scale0, shift0, nterms0, ws2, nterms2):
     """nn.Sequential(convbn_3d(C,C,3,1,1), ReLU, Conv3d(C,1,3,p1)) (models/SemStereo.py:228-234) as two launches whose
     intermediate is channels-last [B,D,H,W,C] (private to the pair: 16-byte stores in the first, 16-byte loads in the head)."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x, scale0, shift0)
     B, C, D, H, W = x.shape
     mid = torch.empty((B, D, H, W, C), dtype=x.dtype, device=x.device)
@@ -345,14 +340,9 @@ def classifier_fused_applies(x, nterms0):
 
 
 def pack_classifier_head_weight(w2):
-    """[1,32,3,3,3] fp32 -> the head's fragments for ss_conv3d_classifier_fused_fwd (three bf16 terms, 6144 bytes)."""
-    w2 = w2.detach().float().contiguous()
-    _lib.require_device(w2)
+    """[1,32,3,3,3] fp32 -> the head's fragments for ss_conv3d_classifier_fused_fwd (three bf16 terms)."""
     assert tuple(w2.shape) == (1, 32, 3, 3, 3)
-    out = torch.empty(3 * 2 * 64 * 8, dtype=torch.int16, device=w2.device)
-    with torch.cuda.device(w2.device):
-        call("ss_pack_classifier_head_weights", ptr(w2), ptr(out))
-    return out
+    return _pack("ss_pack_classifier_head_weights", w2)
 
 
 class PatchedCost:
@@ -373,7 +363,7 @@ def classifier_fused_hip(x, ws0, scale0, shift0, nterms0, head_w, sum_patches=Tr
     """nn.Sequential(convbn_3d(C,32,3,1,1), ReLU, Conv3d(32,1,3,p1)) (models/SemStereo.py:228-234) in one pass over the volume: the
     32-channel intermediate stays in the accumulators, each tile writes a 6 x 6 x 34 patch of head outputs, a second small launch
     adds the patches (conv3d_classifier.hip)."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x, scale0, shift0)
     B, C, D, H, W = x.shape
     ntiles = ((W + 31) // 32) * ((H + 3) // 4) * (D // 4)
@@ -387,23 +377,14 @@ def classifier_fused_hip(x, ws0, scale0, shift0, nterms0, head_w, sum_patches=Tr
 
 def pack_conv2d_weight_bf16s(w, nterms=6):
     """[Cout,Cin,3,3] fp32 -> split fragments for ss_conv2d_bf16s_fwd (three bf16 terms, or two scaled fp16 terms: nterms 19)."""
-    w = w.detach().float().contiguous()
-    _lib.require_device(w)
     Cout, Cin = w.shape[0], w.shape[1]
     assert tuple(w.shape[2:]) == (3, 3)
-    with torch.cuda.device(w.device):
-        if nterms == 19:
-            out = torch.empty(((Cin + 7) // 8) * 5 * 2 * 2 * Cout * 8 + 2 * Cout, dtype=torch.int16, device=w.device)
-            call("ss_pack_conv2d_weights_f16s", ptr(w), ptr(out), Cout, Cin)
-        else:
-            out = torch.empty(((Cin + 7) // 8) * 5 * 3 * 2 * Cout * 8, dtype=torch.int16, device=w.device)
-            call("ss_pack_conv2d_weights_bf16s", ptr(w), ptr(out), Cout, Cin)
-    return out
+    return _pack("ss_pack_conv2d_weights_f16s" if nterms == 19 else "ss_pack_conv2d_weights_bf16s", w, Cout, Cin)
 
 
 def conv2d_bf16s_hip(x, wsplit, Cout, scale, shift, relu, nterms, residual=None):
     """Conv2d(k3, s1, p1, bias=False) + affine + optional residual / ReLU on the split-bf16 engine."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x, scale, shift, residual)
     B, Cin, H, W = x.shape
     out = torch.empty((B, Cout, H, W), dtype=x.dtype, device=x.device)
@@ -500,27 +481,21 @@ def _is_deconv_k4s2(conv):
 def pack_deconv2d_weight(w):
     """ConvTranspose2d weight [Cin,Cout,4,4] fp32 -> the fragments of ss_deconv2d_bf16s_fwd (two scaled fp16 terms per parity class +
     the per-channel inverse scales; int16 tensor, 16-B aligned)."""
-    w = w.detach().float().contiguous()
-    _lib.require_device(w)
     Cin, Cout = w.shape[0], w.shape[1]
     assert tuple(w.shape[2:]) == (4, 4)
-    nct = (Cout + 31) // 32
-    out = torch.empty(((Cin + 7) // 8) * nct * 16 * 64 * 8 + 2 * 32 * nct, dtype=torch.int16, device=w.device)
-    with torch.cuda.device(w.device):
-        call("ss_pack_deconv2d_weights_f16s", ptr(w), ptr(out), Cin, Cout)
-    return out
+    return _pack("ss_pack_deconv2d_weights_f16s", w, Cin, Cout)
 
 
 def deconv2d_bf16s_hip(x, wsplit, Cout, scale, shift, relu, xb=None):
     """ConvTranspose2d(k4, s2, p1) + affine + optional ReLU on the two-term fp16 engine; with `xb` both inputs in one launch
     (-> [2B,Cout,2H,2W], first B: x's)."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x, xb, scale, shift)
     B, Cin, H, W = x.shape
     out = torch.empty(((2 if xb is not None else 1) * B, Cout, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
     with torch.cuda.device(dev):
         if xb is not None:
-            xb = xb if xb.is_contiguous() else xb.contiguous()
+            xb = _c(xb)
             assert xb.shape == x.shape
             call("ss_deconv2d_bf16s_pair_fwd", ptr(x), ptr(xb), ptr(wsplit), ptr(scale), ptr(shift), ptr(out), B, Cin, H, W, Cout,
                  int(relu), 19)
@@ -560,27 +535,21 @@ def _is_conv_k1(conv):
 def pack_conv2d_k1_weight(w):
     """Conv2d weight [Cout,Cin,1,1] (or [Cout,Cin]) fp32 -> the fragments of ss_conv2d_k1_f16s_fwd (two scaled fp16 terms + the
     per-channel inverse scales; int16 tensor, 16-B aligned)."""
-    w = w.detach().float().contiguous()
-    _lib.require_device(w)
     Cout, Cin = w.shape[0], w.shape[1]
     assert w.numel() == Cout * Cin
-    nmt = (Cout + 31) // 32
-    out = torch.empty(((Cin + 31) // 32) * nmt * 256 * 8 + 2 * 32 * nmt, dtype=torch.int16, device=w.device)
-    with torch.cuda.device(w.device):
-        call("ss_pack_conv2d_k1_weights_f16s", ptr(w), ptr(out), Cout, Cin)
-    return out
+    return _pack("ss_pack_conv2d_k1_weights_f16s", w, Cout, Cin)
 
 
 def conv2d_k1_f16s_hip(x, wsplit, Cout, scale, shift, relu, xb=None):
     """Conv2d(1x1) + affine + optional ReLU on the two-term fp16 engine; with `xb` both inputs in one launch (-> [2B,Cout,H,W],
     first B: x's)."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x, xb, scale, shift)
     B, Cin, H, W = x.shape
     out = torch.empty(((2 if xb is not None else 1) * B, Cout, H, W), dtype=x.dtype, device=x.device)
     with torch.cuda.device(dev):
         if xb is not None:
-            xb = xb if xb.is_contiguous() else xb.contiguous()
+            xb = _c(xb)
             assert xb.shape == x.shape
             call("ss_conv2d_k1_f16s_pair_fwd", ptr(x), ptr(xb), ptr(wsplit), ptr(scale), ptr(shift), ptr(out), B, Cin, H * W, Cout,
                  int(relu))
@@ -605,19 +574,14 @@ def run_conv2d_k1(owner, key, conv, bn, x, relu, xb=None):
 
 def pack_seghead_weight(w):
     """conv1.conv.weight [32,Cin,3,3] fp32 -> the fragments of ss_seghead_logits_fwd (int16 tensor, 16-B aligned)."""
-    w = w.detach().float().contiguous()
-    _lib.require_device(w)
     Cin = w.shape[1]
     assert tuple(w.shape) == (32, Cin, 3, 3) and Cin % 8 == 0
-    out = torch.empty((Cin // 8) * 640 * 8 + 2 * 32, dtype=torch.int16, device=w.device)
-    with torch.cuda.device(w.device):
-        call("ss_pack_seghead_weights_f16s", ptr(w), ptr(out), Cin)
-    return out
+    return _pack("ss_pack_seghead_weights_f16s", w, Cin)
 
 
 def bilinear_up2_hip(x):
     """F.interpolate(x, size=(2H, 2W), mode="bilinear", align_corners=False) of a [B,C,H,W] fp32 map."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x)
     B, C, H, W = x.shape
     out = torch.empty((B, C, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
@@ -650,7 +614,7 @@ def run_seghead(owner, head, x):
         return (pack_seghead_weight(a.conv.weight), sc, sh, b.weight.detach().float().reshape(b.out_channels, 32).contiguous(),
                 b.bias.detach().float().contiguous())
     ws, scale, shift, w2, bias = _cache(owner).get("seghead_f16s", srcs, build)
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x, scale, shift, w2, bias)
     B, Cin, H, W = x.shape
     logits = torch.empty((B, b.out_channels, H, W), dtype=x.dtype, device=x.device)
@@ -663,18 +627,9 @@ def run_seghead(owner, head, x):
 def pack_head_weight_bf16s(w, nterms=6):
     """[1,Cin,3,3,3] fp32 -> split fragments (taps as matrix rows) for ss_conv3d_head_bf16s_fwd: three bf16 terms (nterms 6 / 3)
     or two scaled fp16 terms + the inverse scale (nterms 19)."""
-    w = w.detach().float().contiguous()
-    _lib.require_device(w)
     Cin = w.shape[1]
     assert w.shape[0] == 1 and tuple(w.shape[2:]) == (3, 3, 3) and Cin % 16 == 0
-    with torch.cuda.device(w.device):
-        if nterms == 19:
-            out = torch.empty((Cin // 16) * 2 * 2 * 32 * 8 + 8, dtype=torch.int16, device=w.device)
-            call("ss_pack_conv3d_head_weights_f16s", ptr(w), ptr(out), Cin)
-        else:
-            out = torch.empty((Cin // 16) * 3 * 2 * 32 * 8, dtype=torch.int16, device=w.device)
-            call("ss_pack_conv3d_head_weights_bf16s", ptr(w), ptr(out), Cin)
-    return out
+    return _pack("ss_pack_conv3d_head_weights_f16s" if nterms == 19 else "ss_pack_conv3d_head_weights_bf16s", w, Cin)
 
 
 #: SS_HEAD_F16=1: the 32 -> 1 classifier heads on two fp16 terms (3 products, a block exponent per input row) instead of three
@@ -689,7 +644,7 @@ def _head_nterms():
 
 def conv3d_head_bf16s_hip(x, wsplit, scale, shift, relu, nterms):
     """Conv3d(C, 1, 3, padding=1) + affine (+ReLU) on the split-bf16 engine (conv3d_head.hip)."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x, scale, shift)
     B, Cin, D, H, W = x.shape
     out = torch.empty((B, 1, D, H, W), dtype=x.dtype, device=x.device)
@@ -701,19 +656,14 @@ def conv3d_head_bf16s_hip(x, wsplit, scale, shift, relu, nterms):
 
 def pack_pointwise_weight_bf16s(w):
     """[Cout,Cin] (or [Cout,Cin,1,1,1]) fp32 -> split-bf16 fragments for ss_conv3d_pointwise_bf16s_fwd."""
-    w = w.detach().float().reshape(w.shape[0], w.shape[1]).contiguous()
-    _lib.require_device(w)
-    Cout, Cin = w.shape
+    Cout, Cin = w.shape[0], w.shape[1]
     assert Cin % 16 == 0
-    out = torch.empty(((Cout + 31) // 32) * (Cin // 16) * 3 * 2 * 32 * 8, dtype=torch.int16, device=w.device)
-    with torch.cuda.device(w.device):
-        call("ss_pack_pointwise_weights_bf16s", ptr(w), ptr(out), Cout, Cin)
-    return out
+    return _pack("ss_pack_pointwise_weights_bf16s", w.reshape(Cout, Cin), Cout, Cin)
 
 
 def conv3d_pointwise_bf16s_hip(x, wsplit, Cout, scale, shift, relu, nterms):
     """1x1x1 Conv3d / Linear over channels + affine (+ReLU) on the split-bf16 engine; x [B,Cin,*spatial]."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _c(x)
     dev = _lib.require_device(x, scale, shift)
     B, Cin = x.shape[0], x.shape[1]
     out = torch.empty((B, Cout) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)

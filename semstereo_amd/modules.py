@@ -33,6 +33,7 @@ from . import train as T
 from . import train_decoder as TD
 from . import train_heads as TH
 from . import train_ssr as TS
+from ._host import _c
 from ._lib import call, ptr
 # the functional layer (engine.py) and the training convolutions (train_layers.py) under their historical names: `modules.X`
 # keeps resolving for every function; the SWITCHES are engine.py's (see __getattr__ at the end of this file)
@@ -244,7 +245,7 @@ class attention_block(nn.Module):
         x = dfr.real(x)
         if _inference(self, x) and self.hip_supported():
             PATH_COUNTS["hip"] += 1
-            x = x if x.is_contiguous() else x.contiguous()
+            x = _c(x)
             dev = _lib.require_device(x)
             B, C, D, H, W = x.shape
             assert C == self.dim_3d and D % self.block[0] == 0
@@ -532,7 +533,7 @@ class DepthwisePatch(nn.Conv3d):
             x = x.value()
         if _inference(self, x, gate_logits):
             PATH_COUNTS["hip"] += 1
-            x = x if x.is_contiguous() else x.contiguous()
+            x = _c(x)
             dev = _lib.require_device(x, gate_logits)
             B, C, D, H, W = x.shape
             w = self.weight.detach()
@@ -591,7 +592,7 @@ class channelAtt(nn.Module):
             if prm is not None and im.shape[1] * im.shape[2] * im.shape[3] * 4 < 2 ** 31:     # (the kernel's 32-bit offsets per element)
                 PATH_COUNTS["hip"] += 1
                 w1, sc, sh, w2, b2 = prm
-                im = im if im.is_contiguous() else im.contiguous()
+                im = _c(im)
                 dev = _lib.require_device(im)
                 B, Cin, H, W = im.shape
                 c1, c2 = self.im_att[0].conv, self.im_att[1]
@@ -691,7 +692,7 @@ class SSR_upsample(nn.Module):
         depth_low, weights, pred_label = dfr.real(depth_low), dfr.real(weights), dfr.real(pred_label)
         if _inference(self, depth_low, weights, pred_label) and self.num_classes == 6:
             PATH_COUNTS["hip"] += 1
-            depth_low, weights, pred_label = [t if t.is_contiguous() else t.contiguous() for t in (depth_low, weights, pred_label)]
+            depth_low, weights, pred_label = [_c(t) for t in (depth_low, weights, pred_label)]
             dev = _lib.require_device(depth_low, weights, pred_label)
             b, c, h, w = depth_low.shape
             assert c == 1 and weights.shape == (b, self.num_classes, 4 * h, 4 * w) and pred_label.shape == weights.shape

@@ -514,20 +514,11 @@ def stem_left_fused(left, wsplit, att, Cout, nterms=6):
     return out
 
 
-#: int16 elements of ss_pack_stem_left_weights_f16s' result: 4 channel groups x 9 shifts x 2 K-steps x 2 terms x 64 lanes x 8 fp16,
-#: then the 4 x 9 x 24 inverse scales as floats
-STEM_LEFT_MFMA_PACKED = 4 * 9 * 2 * 2 * 64 * 8 + 2 * 4 * 9 * 24
-
-
 def pack_stem_left_weights_f16s(wl):
     """Left-half weights [32, 32, 27] fp32 -> the fragments of stem_left_mfma (int16 tensor, 16-B aligned)."""
-    wl = _c(wl.detach().float())
-    dev = _lib.require_device(wl)
+    from .engine import _pack                                  # (engine imports this module)
     assert tuple(wl.shape) == (32, 32, 27)
-    out = torch.empty(STEM_LEFT_MFMA_PACKED, dtype=torch.int16, device=wl.device)
-    with torch.cuda.device(dev):
-        call("ss_pack_stem_left_weights_f16s", ptr(wl), ptr(out), 32, 32)
-    return out
+    return _pack("ss_pack_stem_left_weights_f16s", wl, 32, 32)
 
 
 def stem_left_mfma(left, wsplit, att, Cout):

@@ -50,15 +50,9 @@ def _count():
 
 def pack_conv2d_k4s2_weight(w):
     """[Cout,Cin,4,4] fp32 (a ConvTranspose2d's own [its Cin, its Cout, 4, 4]) -> the fragments of ss_conv2d_k4s2_f16s_fwd."""
-    w = T._c(w.detach().float())
-    _lib.require_device(w)
     Cout, Cin = w.shape[0], w.shape[1]
     assert tuple(w.shape[2:]) == (4, 4)
-    nct = (Cout + 31) // 32
-    out = torch.empty(((Cin + 7) // 8) * nct * 16 * 64 * 8 + 2 * 32 * nct, dtype=torch.int16, device=w.device)
-    with torch.cuda.device(w.device):
-        E.call("ss_pack_conv2d_k4s2_weights_f16s", ptr(w), ptr(out), Cout, Cin)
-    return out
+    return E._pack("ss_pack_conv2d_k4s2_weights_f16s", w, Cout, Cin)
 
 
 def conv2d_k4s2_hip(g, wsplit, Cout):

@@ -11,6 +11,7 @@ import torch.nn as nn
 from . import _lib
 from . import engine as E
 from . import train as T
+from ._host import _c
 from ._lib import call, ptr
 from .engine import (PATH_COUNTS, conv3d_bf16s_hip, conv3d_head_bf16s_hip, conv3d_hip, deconv3d_bf16s_hip, deconv3d_hip,
                      pack_conv_weight, pack_conv_weight_bf16s, pack_deconv_weight_bf16s, pack_head_weight_bf16s)
@@ -27,8 +28,8 @@ WGRAD_ENGINE = os.environ.get("SS_WGRAD_ENGINE", "bf16x6")
 def conv3d_wgrad_hip(grad_out, x, Cout, Cin, stride):
     """dW [Cout,Cin,3,3,3] of a 3x3x3, padding-1 Conv3d: grad_out [B,Cout,Do,Ho,Wo], x [B,Cin,D,H,W] (conv3d_wgrad_bf16s.hip;
     WGRAD_ENGINE = "f32": conv3d_wgrad.hip)."""
-    grad_out = grad_out if grad_out.is_contiguous() else grad_out.contiguous()
-    x = x if x.is_contiguous() else x.contiguous()
+    grad_out = _c(grad_out)
+    x = _c(x)
     dev = _lib.require_device(grad_out, x)
     B, _, D, H, W = x.shape
     gw = torch.empty((Cout, Cin, 3, 3, 3), dtype=x.dtype, device=x.device)
@@ -68,7 +69,7 @@ class _Conv3dK3(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, stride):
-        x = x if x.is_contiguous() else x.contiguous()
+        x = _c(x)
         ctx.save_for_backward(x, w)
         ctx.stride = stride
         return _conv_k3_forward(x, w.detach(), stride)
@@ -76,7 +77,7 @@ class _Conv3dK3(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
-        g = g if g.is_contiguous() else g.contiguous()
+        g = _c(g)
         gx = gw = None
         if ctx.needs_input_grad[0]:
             if ctx.stride == 1:
@@ -95,14 +96,14 @@ class _Deconv3dK3(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w):
-        x = x if x.is_contiguous() else x.contiguous()
+        x = _c(x)
         ctx.save_for_backward(x, w)
         return _deconv_k3_forward(x, w.detach())
 
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
-        g = g if g.is_contiguous() else g.contiguous()
+        g = _c(g)
         gx = gw = None
         if ctx.needs_input_grad[0]:
             gx = _conv_k3_forward(g, w.detach(), 2)
