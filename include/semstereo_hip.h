@@ -549,6 +549,14 @@ int ss_deconv3d_fwd(const float* in, const float* wpack, const float* scale, con
 int ss_deconv3d_bf16s_fwd(const float* in, const void* wsplit, const float* shift, const float* skip,
                           const void* skip_wsplit, float* out, int B, int Cin, int D, int H, int W, int Cout,
                           int Cs, int relu, int nterms, ss_stream_t stream);
+/* ... preceded by a 1x1x1 conv WITH BIAS that has been folded into it (hourglass.forward: attention_block.final1x1 into
+ * conv5): wsplit packs the composed weights W'[ci][tap][co] = sum_m Wo[m][ci] W5[m][tap][co] (BN scale folded), and the bias,
+ * carried through the transposed conv, is a constant per output channel AND border case of the output position --
+ * shift27 [27][Cout], row (cd * 3 + ch) * 3 + cw with per axis 0 = even output index, 1 = odd interior, 2 = the last odd
+ * index 2N - 1 -- with the layer's own common shift already added.  The skip projection is required. */
+int ss_deconv3d_bf16s_shift27_fwd(const float* in, const void* wsplit, const float* shift27, const float* skip,
+                                  const void* skip_wsplit, float* out, int B, int Cin, int D, int H, int W, int Cout,
+                                  int Cs, int relu, int nterms, ss_stream_t stream);
 int ss_pack_deconv3d_weights_bf16s(const float* wpack, void* wsplit, int Cin, int Cout, int ntaps, ss_stream_t stream);
 int ss_pack_deconv3d_weights_bf16s_bytes(int Cin, int Cout, int ntaps, long long* bytes);
 /* Two-term fp16 form of the MAIN weights (ntaps = 27) for nterms = 19 of ss_deconv3d_bf16s_fwd -- the block-floating
@@ -597,6 +605,13 @@ int ss_window_attention_fwd(const float* x, const float* wqkv_t, const float* bq
  * ss_conv3d_fwd.  One workgroup per (window, 4 heads). */
 int ss_window_attention_core_fwd(const float* qkv, const float* bqkv, float* y, int B, int C, int D, int H,
                                  int W, int heads, int bd, int bh, int bw, ss_stream_t stream);
+/* The core with the qkv_3d projection inside: x [B,C,D,H,W] is the block's input, wqkv_split the [3C,C] weight packed by
+ * ss_pack_pointwise_weights_bf16s, nterms 6 or 3 as for ss_conv3d_pointwise_bf16s_fwd.  Each (window, 4 heads) workgroup
+ * projects its own q/k/v slab with that launch's arithmetic (same fragments, K-steps and product order), so y holds the
+ * bits of ss_conv3d_pointwise_bf16s_fwd + ss_window_attention_core_fwd without the [B,3C,D,H,W] tensor between them. */
+int ss_window_attention_proj_fwd(const float* x, const void* wqkv_split, const float* bqkv, float* y, int B, int C,
+                                 int D, int H, int W, int heads, int bd, int bh, int bw, int nterms,
+                                 ss_stream_t stream);
 
 /* ---- training side of the 3-D stack (main_us3d.py:186-222): what the matrix-core forward / dgrad / wgrad kernels leave over ---- */
 /* BatchNorm with BATCH statistics + optional ReLU (convbn_3d, models/submodule_other.py:845-848; BasicConv,

@@ -101,7 +101,12 @@ struct DB {
 
 // SPLIT: two workgroups per tile, one per parity-class group (blockIdx.x = 2 * tile + group; fp16 form only); ACCB: chunk-blocked
 // accumulation (fp16 form, SPLIT only: it lives in the registers the split frees)
-template <int TD, int TH, int NTERMS, bool HAS_SKIP, bool SPLIT = false, bool ACCB = false, bool STREAM = false>
+// SHIFT27: `shift` is a table [27][Cout] indexed by the output position's border case, (cd * 3 + ch) * 3 + cw with per axis
+// 0 = even output index (tap 1 alone), 1 = odd interior (taps 0 and 2), 2 = the last odd index 2N - 1 (tap 2 alone: its
+// tap-0 input lies beyond the volume).  It is what a per-channel bias added to the INPUT of the transposed conv becomes at
+// its output: a 1x1x1 conv with bias in front of this layer is then folded into `wsplit` and this table
+// (ss_deconv3d_bf16s_shift27_fwd; hourglass.forward folds attention_block.final1x1 into conv5 this way).
+template <int TD, int TH, int NTERMS, bool HAS_SKIP, bool SPLIT = false, bool ACCB = false, bool STREAM = false, bool SHIFT27 = false>
 __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(const float* __restrict__ in, const uint4* __restrict__ wsplit,
                                                           const float* __restrict__ shift, const float* __restrict__ skip,
                                                           const uint4* __restrict__ skip_wsplit, float* __restrict__ out,
@@ -190,7 +195,7 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
     float* aff = reinterpret_cast<float*>(&lds[MSLOT + 1]);
     if (tid < 32) {
         const int co = min(co0 + tid, Cout - 1);
-        aff[tid] = shift ? shift[co] : 0.0f;
+        aff[tid] = (shift && !SHIFT27) ? shift[co] : 0.0f;
         aff[32 + tid] = F16 ? wunscale[co] : 1.0f;
     }
     // Half of the workgroups project the skip tensor BEFORE the main loop, half after it: a grid whose workgroups all
@@ -493,7 +498,27 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
         }
     }
 
+    // SHIFT27: the workgroup's 27 x 32 shifts, requested before the trailing skip projection and parked over the input tile
+    // (dead since the chunk loop's last barrier) after it
+    constexpr int NT27 = SHIFT27 ? (27 * 32 + 255) / 256 : 1;
+    float t27[NT27];
+    if constexpr (SHIFT27) {
+#pragma unroll
+        for (int i = 0; i < NT27; ++i) {
+            const int e = min(tid + 256 * i, 27 * 32 - 1);
+            t27[i] = shift[(e >> 5) * Cout + min(co0 + (e & 31), Cout - 1)];
+        }
+    }
+
     if (HAS_SKIP && !skip_first) skip_phase();
+
+    if constexpr (SHIFT27) {
+        static_assert(27 * 32 <= MSLOT * 4, "the table fits in the input tile");
+#pragma unroll
+        for (int i = 0; i < NT27; ++i)
+            if (tid + 256 * i < 27 * 32) reinterpret_cast<float*>(lds)[tid + 256 * i] = t27[i];
+        __syncthreads();
+    }
 
     // ---- epilogue: each lane owns the 2x2x2 output cube of its input position.  Buffer stores: a 32-bit per-lane offset
     // per (plane, row) pair of the cube (positions outside the volume parked beyond the buffer: the store is dropped) and
@@ -509,6 +534,17 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
         vo[j] = ok ? (unsigned)((((size_t)(2 * jd + (GP::q(j) >> 1)) * Ho + 2 * jh + (GP::q(j) & 1)) * Wo + 2 * jw) * 4) + 4u * half * ochan_b
                    : 0x80000000u;
     const float floor_v = relu ? 0.f : -__builtin_inff();
+    // SHIFT27: the table rows of this lane's cube, row (j, pw) = the cases of (pd, ph, pw); an odd index is the axis' last where
+    // its input index is
+    int trow[SHIFT27 ? GP::NQ2 : 1][2];
+    if constexpr (SHIFT27) {
+        const int cd = 9 * (1 + (jd == D - 1)), ch = 3 * (1 + (jh == H - 1)), cw = 1 + (jw == W - 1);
+#pragma unroll
+        for (int j = 0; j < GP::NQ2; ++j)
+#pragma unroll
+            for (int pw = 0; pw < 2; ++pw)
+                trow[j][pw] = (((GP::q(j) >> 1) ? cd : 0) + ((GP::q(j) & 1) ? ch : 0) + (pw ? cw : 0)) * 32 + 4 * half;
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int cb = co0 + (r & 3) + 8 * (r >> 2);
@@ -516,8 +552,14 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
         const float sh = aff[(r & 3) + 8 * (r >> 2) + 4 * half];
 #pragma unroll
         for (int j = 0; j < GP::NQ2; ++j) {
-            const float v0 = fmaxf(ss::add_rn(acc[j * 2 + 0][r], sh), floor_v);
-            const float v1 = fmaxf(ss::add_rn(acc[j * 2 + 1][r], sh), floor_v);
+            float sh0 = sh, sh1 = sh;
+            if constexpr (SHIFT27) {
+                const float* tab = reinterpret_cast<const float*>(lds) + (r & 3) + 8 * (r >> 2);
+                sh0 = tab[trow[j][0]];
+                sh1 = tab[trow[j][1]];
+            }
+            const float v0 = fmaxf(ss::add_rn(acc[j * 2 + 0][r], sh0), floor_v);
+            const float v1 = fmaxf(ss::add_rn(acc[j * 2 + 1][r], sh1), floor_v);
 #ifdef SS_EXP_DECONV_NOSTORE          // (timing experiment: one store per lane instead of 64)
             if (r == 0 && j == 0)
 #endif
@@ -599,14 +641,14 @@ __global__ void pack_deconv_weights_f16s_kernel(const float* __restrict__ wpack,
     wsplit[i] = split_weight_f16(x, term);
 }
 
-template <int TD, int TH, int NTERMS, bool HAS_SKIP, bool SPLIT = false, bool ACCB = false, bool STREAM = false>
+template <int TD, int TH, int NTERMS, bool HAS_SKIP, bool SPLIT = false, bool ACCB = false, bool STREAM = false, bool SHIFT27 = false>
 int launch_db(const float* in, const void* wsplit, const float* shift, const float* skip, const void* skip_wsplit, float* out,
               int B, int Cin, int D, int H, int W, int Cout, int Cs, int relu, hipStream_t st) {
     using C = DB<TD, TH, (NTERMS == 6) ? 3 : 2, NTERMS == F16X3, SPLIT ? 15 : 27>;
     const int tiles_w = ss::ceil_div(W, 32), tiles_h = ss::ceil_div(H, TH), tiles_d = ss::ceil_div(D, TD);
     const long long nt = (long long)tiles_w * tiles_h * tiles_d;
     if (nt > 0x7fffffffLL || B > 65535) return SS_ERR_UNSUPPORTED;
-    auto kern = deconv3d_bf16s<TD, TH, NTERMS, HAS_SKIP, SPLIT, ACCB, STREAM>;
+    auto kern = deconv3d_bf16s<TD, TH, NTERMS, HAS_SKIP, SPLIT, ACCB, STREAM, SHIFT27>;
     if (C::LDS_BYTES > 64 * 1024) {
         if (ss::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)C::LDS_BYTES) != SS_OK) return SS_ERR_LAUNCH;
     }
@@ -618,12 +660,15 @@ int launch_db(const float* in, const void* wsplit, const float* shift, const flo
     return ss::check_launch();
 }
 
-template <int TD, int TH>
+// (SHIFT27: with the skip projection only -- the one layer that has a biased 1x1x1 conv folded in has one)
+template <int TD, int TH, bool SHIFT27 = false>
 int launch_db_all(const float* in, const void* wsplit, const float* shift, const float* skip, const void* skip_wsplit,
                   float* out, int B, int Cin, int D, int H, int W, int Cout, int Cs, int relu, int nterms, hipStream_t st) {
-#define SS_DB(NTERMS, HAS_SKIP) launch_db<TD, TH, NTERMS, HAS_SKIP>(in, wsplit, shift, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, st)
+    // (under SHIFT27 the no-skip arms name the skip instantiation too, so none is built without the projection)
+#define SS_DB(NTERMS, HAS_SKIP) launch_db<TD, TH, NTERMS, (HAS_SKIP) || SHIFT27, false, false, false, SHIFT27>(in, wsplit, shift, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, st)
 #define SS_DF(HAS_SKIP, SPLIT, ACCB, STREAM) \
-    launch_db<TD, TH, F16X3, HAS_SKIP, SPLIT, ACCB, STREAM>(in, wsplit, shift, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, st)
+    launch_db<TD, TH, F16X3, (HAS_SKIP) || SHIFT27, SPLIT, ACCB, STREAM, SHIFT27>(in, wsplit, shift, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, st)
+    if (SHIFT27 && skip == nullptr) return SS_ERR_UNSUPPORTED;
     if (nterms == F16X3) {
         // Parity-class groups (r05, Grp<> above), measured alone on the four transposed convs of the 1024^2 pair (hourglass2.conv6 /
         // .conv5, hourglass_att.conv6 / .conv5; profiles/r05_f_deconv_forms.txt): all 8 classes per workgroup 128 / 55 / 38 / 39 us;
@@ -704,4 +749,21 @@ extern "C" int ss_deconv3d_bf16s_fwd(const float* in, const void* wsplit, const 
     if (D >= 2 && H < 4)
         return launch_db_all<2, 2>(in, wsplit, shift, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, nterms, st);
     return launch_db_all<1, 4>(in, wsplit, shift, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, nterms, st);
+}
+
+// ... with the shift as a table over the 27 border cases of an output position (SHIFT27 above): shift27 [27][Cout]
+extern "C" int ss_deconv3d_bf16s_shift27_fwd(const float* in, const void* wsplit, const float* shift27, const float* skip,
+                                             const void* skip_wsplit, float* out, int B, int Cin, int D, int H, int W, int Cout,
+                                             int Cs, int relu, int nterms, ss_stream_t stream) {
+    SS_REQUIRE(in && wsplit && out && shift27 && skip && skip_wsplit && Cs > 0);
+    SS_REQUIRE(B > 0 && Cin > 0 && D > 0 && H > 0 && W > 0 && Cout > 0 && (nterms == 3 || nterms == 6 || nterms == F16X3));
+    SS_REQUIRE((reinterpret_cast<uintptr_t>(wsplit) & 15) == 0 && (reinterpret_cast<uintptr_t>(skip_wsplit) & 15) == 0);
+    if ((reinterpret_cast<uintptr_t>(out) & 7) != 0) return SS_ERR_INVALID;
+    if ((long long)Cin * D * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
+    if ((long long)Cs * 8 * D * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
+    if ((long long)Cout * 8 * D * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
+    hipStream_t st = ss::as_stream(stream);
+    if (D >= 2 && H < 4)
+        return launch_db_all<2, 2, true>(in, wsplit, shift27, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, nterms, st);
+    return launch_db_all<1, 4, true>(in, wsplit, shift27, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, nterms, st);
 }

@@ -35,33 +35,15 @@ struct ACfg {
     static constexpr size_t LDS_BYTES = (size_t)(XS + QKV + YG + FLAGS + WL) * 4;
 };
 
+// The window's tokens -> LDS, channel-major [C][TP] (zeros at padded positions and in the N-tile tail): the first phase of
+// the fused kernel and of the projecting core (window_attention_proj) alike.
 template <int T, int C>
-__global__ __launch_bounds__(256) void window_attention_kernel(
-    const float* __restrict__ x, const float* __restrict__ wqkv_t, const float* __restrict__ bqkv,
-    const float* __restrict__ wout_t, const float* __restrict__ bout, float* __restrict__ out, int D, int H, int W,
-    int bd, int bh, int bw, int nwh, int nww, int use_mask) {
+__device__ __forceinline__ void stage_window_tokens(float* __restrict__ xs, const float* __restrict__ xb, int tid, int wd, int wh,
+                                                    int ww, int H, int W, int bd, int bh, int bw, size_t plane, size_t vol) {
     using A = ACfg<T, C>;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* xs = lds;                 // [C][TP]
-    float* qkv = xs + A::XS;         // [3*32][TP]   rows 0-31 q, 32-63 k, 64-95 v of the current head group
-    float* yg = qkv + A::QKV;        // [32][TP]
-    float* flag = yg + A::YG;        // [TP]  1 = padded position (reference mask semantics)
-    float* wl = flag + A::FLAGS;     // [C][96]  qkv_3d weight rows of the current head group, k-major
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, half = lane >> 5;
-    int wi = blockIdx.x;
-    const int ww = wi % nww; wi /= nww;
-    const int wh = wi % nwh; wi /= nwh;
-    const int wd = wi;
-    const int b = blockIdx.y;
-    const size_t plane = (size_t)H * W, vol = (size_t)D * plane;
-    const float* xb = x + (size_t)b * C * vol;
-
-    // ---- phase 0: window tokens -> LDS (zeros at padded positions and in the N-tile tail) ----
-    if (bw == 4 && (W & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) & 15) == 0)) {
+    if (bw == 4 && (W & 3) == 0 && ((reinterpret_cast<uintptr_t>(xb) & 15) == 0)) {
         // a window row is exactly one aligned float4: C * T/4 quads, loaded in branch-free batches
-        constexpr int NQ = C * (A::TP / 4) / 256;          // quads per thread (12 or 8)
+        constexpr int NQ = C * (A::TP / 4) / 256;          // quads per thread (12 or 8; 6 at half the channels)
         static_assert(C * (A::TP / 4) % 256 == 0, "whole batches");
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
@@ -86,6 +68,33 @@ __global__ __launch_bounds__(256) void window_attention_kernel(
             xs[e] = v;
         }
     }
+}
+
+template <int T, int C>
+__global__ __launch_bounds__(256) void window_attention_kernel(
+    const float* __restrict__ x, const float* __restrict__ wqkv_t, const float* __restrict__ bqkv,
+    const float* __restrict__ wout_t, const float* __restrict__ bout, float* __restrict__ out, int D, int H, int W,
+    int bd, int bh, int bw, int nwh, int nww, int use_mask) {
+    using A = ACfg<T, C>;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* xs = lds;                 // [C][TP]
+    float* qkv = xs + A::XS;         // [3*32][TP]   rows 0-31 q, 32-63 k, 64-95 v of the current head group
+    float* yg = qkv + A::QKV;        // [32][TP]
+    float* flag = yg + A::YG;        // [TP]  1 = padded position (reference mask semantics)
+    float* wl = flag + A::FLAGS;     // [C][96]  qkv_3d weight rows of the current head group, k-major
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, half = lane >> 5;
+    int wi = blockIdx.x;
+    const int ww = wi % nww; wi /= nww;
+    const int wh = wi % nwh; wi /= nwh;
+    const int wd = wi;
+    const int b = blockIdx.y;
+    const size_t plane = (size_t)H * W, vol = (size_t)D * plane;
+    const float* xb = x + (size_t)b * C * vol;
+
+    // ---- phase 0: window tokens -> LDS (zeros at padded positions and in the N-tile tail) ----
+    stage_window_tokens<T, C>(xs, xb, tid, wd, wh, ww, H, W, bd, bh, bw, plane, vol);
     for (int t = tid; t < A::TP; t += 256) {
         float f = 0.f;
         if (t < T) {
@@ -249,6 +258,11 @@ __global__ __launch_bounds__(256) void window_attention_kernel(
 // workgroup per window: 128-256 of them, one wave per SIMD).  A padded token's q/k/v is the Linear bias
 // (the reference pads with zeros before qkv_3d, models/submodule_other.py:797-803).
 template <int T, int C>
+__device__ __forceinline__ void attend_head_group(float* __restrict__ qkv, const float* __restrict__ flag, const unsigned (&vmax_w)[4],
+                                                  float* __restrict__ y, int b, int g, int wd, int wh, int ww, int D, int H, int W,
+                                                  int bd, int bh, int bw, int use_mask);
+
+template <int T, int C>
 __global__ __launch_bounds__(256) void window_attention_core(const float* __restrict__ qkv_in, const float* __restrict__ bqkv,
                                                               float* __restrict__ y, int D, int H, int W, int bd, int bh,
                                                               int bw, int nwh, int nww, int use_mask) {
@@ -257,7 +271,6 @@ __global__ __launch_bounds__(256) void window_attention_core(const float* __rest
     __shared__ __attribute__((aligned(16))) float qkv[3 * 32 * A::TP];     // rows 0-31 q, 32-63 k, 64-95 v of this head group
     __shared__ float flag[A::TP];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, half = lane >> 5;
     constexpr int NGROUPS = C / (HG * HD);
     int wi = blockIdx.x;
     const int g = wi % NGROUPS; wi /= NGROUPS;
@@ -308,7 +321,19 @@ __global__ __launch_bounds__(256) void window_attention_core(const float* __rest
         flag[t] = ((wh * bh + ih >= H) || (ww * bw + iw >= W)) ? 1.f : 0.f;
     }
     __syncthreads();
+    attend_head_group<T, C>(qkv, flag, vmax_w, y, b, g, wd, wh, ww, D, H, W, bd, bh, bw, use_mask);
+}
 
+// softmax(q k^T) v of one (window, group of 4 heads) whose q/k/v slab [96][T], pad flags and per-wave V maxima are in LDS
+// (and visible: the caller has passed a barrier): everything of the core after its loads, shared by its two forms.
+template <int T, int C>
+__device__ __forceinline__ void attend_head_group(float* __restrict__ qkv, const float* __restrict__ flag, const unsigned (&vmax_w)[4],
+                                                  float* __restrict__ y, int b, int g, int wd, int wh, int ww, int D, int H, int W,
+                                                  int bd, int bh, int bw, int use_mask) {
+    using A = ACfg<T, C>;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, half = lane >> 5;
+    const size_t plane = (size_t)H * W, vol = (size_t)D * plane;
     const float scale = 0.35355339059327379f;    // 8 ** -0.5
     // block exponent of V (see the P V product below): max -> [2^14, 2^15); a non-finite V makes the scale non-finite
     const int e_v = workgroup_exponent(vmax_w);
@@ -413,6 +438,134 @@ __global__ __launch_bounds__(256) void window_attention_core(const float* __rest
     }
 }
 
+// The core with the q/k/v projection inside (ss_window_attention_proj_fwd): instead of reading a q/k/v tensor that a
+// pointwise_bf16s launch (conv3d_head.hip) wrote, the workgroup stages its window's tokens of x ([C][T] fp32, zeros at padded
+// positions: the projection of a zero token is the bias, what the core substitutes there) and projects the 96 features of
+// its head group itself -- M = 96 (q, k, v rows g*32 .. +31), N = T, K = C on the bf16 matrix core, from the SAME packed
+// fragments (ss_pack_pointwise_weights_bf16s), with the same K-step (16 channels, lane half h = channels 8h .. 8h+7), the same
+// products in the same order and the same `acc + bias` as pointwise_bf16s<8, NTERMS>: the slab holds the bits that launch
+// writes.  The tiles stay in accumulators (at most 3 per wave) until every wave has finished reading x, then the slab
+// [96][T] goes over the dead x tile; x is parked as fp32 (not pre-split), in KH stages of C / KH channels (launch_attn_proj).
+template <int T, int C, int NTERMS, int KH>
+__global__ __launch_bounds__(256, KH == 2 ? 4 : 3) void window_attention_proj(const float* __restrict__ x, const uint4* __restrict__ wsplit,
+                                                              const float* __restrict__ bqkv, float* __restrict__ y, int D, int H,
+                                                              int W, int bd, int bh, int bw, int nwh, int nww, int use_mask) {
+    using A = ACfg<T, C>;
+    static_assert(A::TP == T && C % (32 * KH) == 0 && (KH == 1 || KH == 2), "whole 32-token tiles, whole K-steps per stage");
+    constexpr int NC = (NTERMS == 6) ? 3 : 2;
+    constexpr int KS = C / 16;
+    constexpr int CH = C / KH;                                 // channels of x staged at a time
+    __shared__ __attribute__((aligned(16))) float buf[(CH > 96 ? CH : 96) * A::TP];      // x [CH][TP], then q/k/v [96][TP]
+    __shared__ float flag[A::TP];
+    __shared__ unsigned vmax_w[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, half = lane >> 5;
+    constexpr int NGROUPS = C / (HG * HD);
+    int wi = blockIdx.x;
+    const int g = wi % NGROUPS; wi /= NGROUPS;
+    const int ww = wi % nww; wi /= nww;
+    const int wh = wi % nwh; wi /= nwh;
+    const int wd = wi;
+    const int b = blockIdx.y;
+    const size_t plane = (size_t)H * W, vol = (size_t)D * plane;
+
+    for (int t = tid; t < A::TP; t += 256) {
+        const int iw = t % bw, ih = (t / bw) % bh;
+        flag[t] = ((wh * bh + ih >= H) || (ww * bw + iw >= W)) ? 1.f : 0.f;
+    }
+    // tile u = (mt, nt) = (u / NTL, u % NTL) of the slab belongs to wave u % 4: mt 0 = q, 1 = k, 2 = v
+    constexpr int NU = (3 * A::NTL + 3) / 4;
+    f32x16 acc[NU];
+#pragma unroll
+    for (int i = 0; i < NU; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    // KH = 2: x in two stages of C / 2 channels through the same LDS (the K-steps run in the same order: the same sums)
+#pragma unroll
+    for (int kh = 0; kh < KH; ++kh) {
+        if (kh > 0) __syncthreads();                           // every wave has read the previous stage
+        stage_window_tokens<T, CH>(buf, x + ((size_t)b * C + kh * CH) * vol, tid, wd, wh, ww, H, W, bd, bh, bw, plane, vol);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NU; ++i) {
+            const int u = wave + 4 * i;                        // (wave-uniform)
+            if (u >= 3 * A::NTL) continue;
+            const int mt = u / A::NTL, nt = u % A::NTL;
+            const uint4* ap = wsplit + (size_t)(mt * (C / 32) + g) * KS * 3 * 64 + half * 32 + l31;
+            const float* bp = buf + 8 * half * A::TP + nt * 32 + l31;
+#pragma unroll
+            for (int k = 0; k < KS / KH; ++k) {
+                const int ks = kh * (KS / KH) + k;
+                bf16x8 a[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) a[c] = __builtin_bit_cast(bf16x8, ap[(ks * 3 + c) * 64]);
+                unsigned bh_[4], bm_[4], bl_[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    split3_pk(bp[(k * 16 + 2 * j) * A::TP], bp[(k * 16 + 2 * j + 1) * A::TP], bh_[j], bm_[j], bl_[j]);
+                const bf16x8 h8 = __builtin_bit_cast(bf16x8, make_uint4(bh_[0], bh_[1], bh_[2], bh_[3]));
+                const bf16x8 m8 = __builtin_bit_cast(bf16x8, make_uint4(bm_[0], bm_[1], bm_[2], bm_[3]));
+                if (NTERMS == 6) {
+                    const bf16x8 l8 = __builtin_bit_cast(bf16x8, make_uint4(bl_[0], bl_[1], bl_[2], bl_[3]));
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], m8, acc[i], 0, 0, 0);
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], l8, acc[i], 0, 0, 0);
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[NC - 1], h8, acc[i], 0, 0, 0);
+                }
+                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], m8, acc[i], 0, 0, 0);
+                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], h8, acc[i], 0, 0, 0);
+                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], h8, acc[i], 0, 0, 0);
+            }
+        }
+    }
+    float bias[NU][16];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+        const int u = wave + 4 * i;
+        if (u >= 3 * A::NTL) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) bias[i][r] = bqkv[(u / A::NTL) * C + g * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
+    }
+    __syncthreads();                                           // every wave has read its last token of x
+    float vm = 0.f;                                            // |max| of this thread's share of the V rows (64-95)
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+        const int u = wave + 4 * i;
+        if (u >= 3 * A::NTL) continue;
+        const int mt = u / A::NTL, nt = u % A::NTL;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float v = ss::add_rn(acc[i][r], bias[i][r]);
+            buf[(mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * A::TP + nt * 32 + l31] = v;
+            if (mt == 2) vm = fmaxf(vm, fabsf(v));
+        }
+    }
+    {
+        const unsigned wm = wave_max_bits(__float_as_uint(vm));
+        if (lane == 0) vmax_w[wave] = wm;
+    }
+    __syncthreads();
+    attend_head_group<T, C>(buf, flag, vmax_w, y, b, g, wd, wh, ww, D, H, W, bd, bh, bw, use_mask);
+}
+
+// T = 96: x in one stage (48 KB: three workgroups per CU) or in two (the slab's 36 KB and 127 registers: four, as the plain
+// core, and the 1024 workgroups of a [128,6,64,64] volume are resident at once).  Measured alone on that volume, three
+// interleaved repeats: 58.5-59.7 us in one stage, 55.7-56.1 in two (profiles/attn_onelaunch_ab.txt).  T = 64 fits four
+// workgroups in one stage.
+#ifndef SS_ATTN_PROJ_KH96
+#define SS_ATTN_PROJ_KH96 2
+#endif
+template <int T, int NTERMS>
+int launch_attn_proj(const float* x, const void* wsplit, const float* bqkv, float* y, int B, int D, int H, int W, int bd, int bh,
+                     int bw, hipStream_t st) {
+    const int nwd = D / bd, nwh = ss::ceil_div(H, bh), nww = ss::ceil_div(W, bw);
+    const int use_mask = (H % bh != 0) && (W % bw != 0);      // the reference's "-0:" quirk, see launch_attn
+    const long long nblk = (long long)nwd * nwh * nww * (128 / (HG * HD));
+    if (nblk > 0x7fffffffLL || B > 65535) return SS_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((window_attention_proj<T, 128, NTERMS, T == 96 ? SS_ATTN_PROJ_KH96 : 1>), dim3((unsigned)nblk, B), dim3(256), 0, st, x,
+                       reinterpret_cast<const uint4*>(wsplit), bqkv, y, D, H, W, bd, bh, bw, nwh, nww, use_mask);
+    return ss::check_launch();
+}
+
 template <int T>
 int launch_attn_core(const float* qkv, const float* bqkv, float* y, int B, int D, int H, int W, int bd, int bh, int bw,
                      hipStream_t st) {
@@ -470,5 +623,25 @@ extern "C" int ss_window_attention_core_fwd(const float* qkv, const float* bqkv,
     hipStream_t st = ss::as_stream(stream);
     if (T == 64) return launch_attn_core<64>(qkv, bqkv, y, B, D, H, W, bd, bh, bw, st);
     if (T == 96) return launch_attn_core<96>(qkv, bqkv, y, B, D, H, W, bd, bh, bw, st);
+    return SS_ERR_UNSUPPORTED;
+}
+
+extern "C" int ss_window_attention_proj_fwd(const float* x, const void* wqkv_split, const float* bqkv, float* y, int B, int C,
+                                            int D, int H, int W, int heads, int bd, int bh, int bw, int nterms,
+                                            ss_stream_t stream) {
+    SS_REQUIRE(x && wqkv_split && bqkv && y);
+    SS_REQUIRE(B > 0 && C > 0 && D > 0 && H > 0 && W > 0 && heads > 0 && bd > 0 && bh > 0 && bw > 0);
+    SS_REQUIRE(D % bd == 0 && (nterms == 3 || nterms == 6));
+    SS_REQUIRE((reinterpret_cast<uintptr_t>(wqkv_split) & 15) == 0);
+    if (C != 128 || heads != 16) return SS_ERR_UNSUPPORTED;
+    const int T = bd * bh * bw;
+    hipStream_t st = ss::as_stream(stream);
+#define SS_AP(TV)                                                                                                     \
+    if (T == TV)                                                                                                      \
+        return nterms == 6 ? launch_attn_proj<TV, 6>(x, wqkv_split, bqkv, y, B, D, H, W, bd, bh, bw, st)              \
+                           : launch_attn_proj<TV, 3>(x, wqkv_split, bqkv, y, B, D, H, W, bd, bh, bw, st);
+    SS_AP(64)
+    SS_AP(96)
+#undef SS_AP
     return SS_ERR_UNSUPPORTED;
 }

@@ -869,8 +869,46 @@ def stem_of_broadcast_and_volume(stem, left, att, right_vol, gate=None):
     (stem_volume_half) (models/SemStereo.py:241-244, 316-320).  Split-bf16 engines, inference only."""
     return stem_volume_half(stem, right_vol, stem_broadcast_half(stem, left, att), gate)
 
-ATTENTION_FORM = os.environ.get("SS_ATTENTION", "split")      # "split" (3 launches) | "fused" (one kernel per window)
+#: "split" (projection, per-(window, 4 heads) core, projection: 3 launches) | "proj" (the core projects its own q/k/v slab with the
+#: split form's arithmetic -- same bits -- so the qkv launch and its [B,3C,D,H,W] tensor are gone) | "fused" (one kernel per window)
+ATTENTION_FORM = os.environ.get("SS_ATTENTION", "proj")
+#: hourglass.forward (inference, split-engine transposed conv): attention_block.final1x1 composed into conv5's packed weights and a
+#: 27-case shift table (fold_pointwise_into_deconv) instead of a launch of its own
+ATTN_FOLD = os.environ.get("SS_ATTN_FOLD", "1") != "0"
+
+
+def fold_pointwise_into_deconv(wo, bo, w5, bn_scale, shift, dtype=torch.float32):
+    """ConvTranspose3d(k3, s2, p1, op1, bias=False)(Conv3d 1x1x1 with bias) as ONE transposed conv: both are linear, so
+         W'[ci, co, tap] = sum_m wo[m, ci] * w5[m, co, tap]
+    and the bias `bo`, carried through the transposed conv, is constant per output channel and BORDER CASE of the output
+    position: from o = 2 i - 1 + k an even output index receives tap 1 alone (case 0), an odd interior one taps 0 and 2 (case 1),
+    the last odd one, 2 N - 1, tap 2 alone (case 2: its tap-0 input lies beyond the volume; with N = 1 it is the only odd index).
+    wo [C, C(,1,1,1)], bo [C], w5 [C, Co, 3, 3, 3], bn_scale / shift [Co] (the BatchNorm scale after the transposed conv and
+    the layer's common shift).  Returns (W' * bn_scale  [C, Co, 3, 3, 3], shift27 [27, Co] with row (cd * 3 + ch) * 3 + cw),
+    computed in float64 and rounded to `dtype` once."""
+    C = w5.shape[0]
+    wo64, w564 = wo.detach().double().reshape(C, -1), w5.detach().double()
+    s64 = bn_scale.detach().double().reshape(1, -1, 1, 1, 1)
+    wf = torch.einsum("mi,moxyz->ioxyz", wo64, w564) * s64
+    bw = torch.einsum("m,moxyz->oxyz", bo.detach().double(), w564) * s64[0]          # [Co, 3, 3, 3]: the bias through each tap
+    valid = torch.tensor([[0., 1., 0.], [1., 0., 1.], [0., 0., 1.]], dtype=torch.float64, device=bw.device)     # [case][tap]
+    t27 = torch.einsum("ax,by,cz,oxyz->abco", valid, valid, valid, bw).reshape(27, -1) + shift.detach().double().reshape(1, -1)
+    return wf.to(dtype).contiguous(), t27.to(dtype).contiguous()
+
+
+def deconv3d_bf16s_shift27_hip(x, wsplit, Cout, shift27, relu, nterms, skip, skip_wsplit):
+    """deconv3d_bf16s_hip with the shift as a table over the 27 border cases of an output position (fold_pointwise_into_deconv)."""
+    x, skip = _c(x), _c(skip)
+    dev = _lib.require_device(x, shift27, skip)
+    B, Cin, D, H, W = x.shape
+    Cs = skip.shape[1]
+    assert skip.shape == (B, Cs, 2 * D, 2 * H, 2 * W) and shift27.shape == (27, Cout) and shift27.is_contiguous()
+    out = torch.empty((B, Cout, 2 * D, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
+    with torch.cuda.device(dev):
+        call("ss_deconv3d_bf16s_shift27_fwd", ptr(x), ptr(wsplit), ptr(shift27), ptr(skip), ptr(skip_wsplit), ptr(out),
+             B, Cin, D, H, W, Cout, Cs, int(relu), int(nterms))
+    return out
 
 #: the names tests / tools may SET on this module; `modules.X` forwards reads of them here
-SWITCHES = ("CONV_ENGINE", "DECONV_F16", "DECONV_MIN_WORKGROUPS", "DECONV_BF16S", "CLASSIFIER_CL", "CLASSIFIER_FUSED", "CLASSIFIER_FOLD", "TRAIN_HIP", "SSR_TRAIN_HIP", "HEADS_TRAIN_HIP", "DECODER_TRAIN_HIP", "CONV2D_WGRAD_HIP", "LOSS_HIP", "METRICS_HIP", "VIS_HIP", "DATA_HIP", "ATTENTION_FORM",
+SWITCHES = ("CONV_ENGINE", "DECONV_F16", "DECONV_MIN_WORKGROUPS", "DECONV_BF16S", "CLASSIFIER_CL", "CLASSIFIER_FUSED", "CLASSIFIER_FOLD", "TRAIN_HIP", "SSR_TRAIN_HIP", "HEADS_TRAIN_HIP", "DECODER_TRAIN_HIP", "CONV2D_WGRAD_HIP", "LOSS_HIP", "METRICS_HIP", "VIS_HIP", "DATA_HIP", "ATTENTION_FORM", "ATTN_FOLD",
             "STEM_LEFT_FUSED", "STEM_LEFT_MFMA", "STEM_PRESPLIT", "STEM_GATHER", "STEM_INPLACE", "HEAD_F16", "CONV2D_HIP", "DECODER_HIP", "HEADS_HIP")

@@ -239,29 +239,44 @@ class attention_block(nn.Module):
         bd, bh, bw = self.block
         return self.dim_3d == 128 and self.num_heads == 16 and bd * bh * bw in (64, 96)
 
-    def forward(self, x):
+    def folds_final(self, x):
+        """Whether forward(x, final=False) applies: the forms that end in a `final1x1` launch of their own, in inference."""
+        return _inference(self, dfr.real(x)) and self.hip_supported() and E.ATTENTION_FORM in ("split", "proj")
+
+    def forward(self, x, final=True):
+        """final=False (hourglass.forward alone, where folds_final(x)): the attended tokens WITHOUT final1x1, which the caller
+        has composed into the layer that follows."""
         # another head count / width / window than the reference's: the same computation as PyTorch ops on the GPU
         # (visible in PATH_COUNTS["torch"]) instead of an SS_ERR_UNSUPPORTED from deep inside forward()
         x = dfr.real(x)
+        assert final or self.folds_final(x)
         if _inference(self, x) and self.hip_supported():
             PATH_COUNTS["hip"] += 1
             x = _c(x)
             dev = _lib.require_device(x)
             B, C, D, H, W = x.shape
             assert C == self.dim_3d and D % self.block[0] == 0
-            if E.ATTENTION_FORM == "split":
+            if E.ATTENTION_FORM in ("split", "proj"):
                 # projection -> per-(window, 4 heads) attention -> projection: three launches that each fill
                 # the chip at batch 1 (the fused kernel has one workgroup per window)
                 wq, bq, wo, bo, bf = self._params_split()
                 nterms = _aux_nterms()
-                if bf:
-                    qkv = conv3d_pointwise_bf16s_hip(x, wq, 3 * C, None, bq, False, nterms)
-                else:
-                    qkv = conv3d_hip(x, wq, None, bq, 1, 1, False)
                 y = torch.empty_like(x)
-                with torch.cuda.device(dev):
-                    call("ss_window_attention_core_fwd", ptr(qkv), ptr(bq), ptr(y), B, C, D, H, W, self.num_heads,
-                         self.block[0], self.block[1], self.block[2])
+                if E.ATTENTION_FORM == "proj" and bf:
+                    # ... two: the core projects its own q/k/v slab from x (the split form's arithmetic, the same bits)
+                    with torch.cuda.device(dev):
+                        call("ss_window_attention_proj_fwd", ptr(x), ptr(wq), ptr(bq), ptr(y), B, C, D, H, W, self.num_heads,
+                             self.block[0], self.block[1], self.block[2], nterms)
+                else:
+                    if bf:
+                        qkv = conv3d_pointwise_bf16s_hip(x, wq, 3 * C, None, bq, False, nterms)
+                    else:
+                        qkv = conv3d_hip(x, wq, None, bq, 1, 1, False)
+                    with torch.cuda.device(dev):
+                        call("ss_window_attention_core_fwd", ptr(qkv), ptr(bq), ptr(y), B, C, D, H, W, self.num_heads,
+                             self.block[0], self.block[1], self.block[2])
+                if not final:
+                    return y
                 if bf:
                     return conv3d_pointwise_bf16s_hip(y, wo, C, None, bo, False, nterms)
                 return conv3d_hip(y, wo, None, bo, 1, 1, False)
@@ -346,14 +361,38 @@ class hourglass(nn.Module):
                     pack_deconv_weight_bf16s(wr) if E.CONV_ENGINE != "f32" else None)
         return _cache(self).get(key + "/" + E.CONV_ENGINE, srcs, build)
 
-    def _up(self, key, deconv_seq, redir_seq, x, skip):
-        wd, wr, shift, wds, wrs = self._up_params(key, deconv_seq, redir_seq)
+    def _up_takes_split_engine(self, key, deconv_seq, redir_seq, x):
+        wd = self._up_params(key, deconv_seq, redir_seq)[0]
         B, _, D, H, W = x.shape
         workgroups = B * D * ((H + 3) // 4) * ((W + 31) // 32) * ((wd.shape[2] + 31) // 32)
         # layers with few workgroups: the exact-fp32 kernel's even/odd-plane split doubles them (see DECONV_MIN_WORKGROUPS)
-        if E.CONV_ENGINE != "f32" and E.DECONV_BF16S and workgroups >= E.DECONV_MIN_WORKGROUPS:
+        return E.CONV_ENGINE != "f32" and E.DECONV_BF16S and workgroups >= E.DECONV_MIN_WORKGROUPS
+
+    def _up(self, key, deconv_seq, redir_seq, x, skip):
+        wd, wr, shift, wds, wrs = self._up_params(key, deconv_seq, redir_seq)
+        if self._up_takes_split_engine(key, deconv_seq, redir_seq, x):
             return deconv3d_bf16s_hip(x, wds, wd.shape[2], shift, True, _deconv_nterms(), skip, wrs)
         return deconv3d_hip(x, wd, shift, relu=True, skip=skip, skip_wpack=wr)
+
+    def _up5_folded_params(self):
+        """conv5 with attention_block.final1x1 composed into it (engine.fold_pointwise_into_deconv): the packed composed weights
+        and the 27-case shift table; the skip projection is `_up_params`' own."""
+        dc, dbn, rbn, fin = self.conv5[0], self.conv5[1], self.redir2[1], self.attention_block.final1x1
+        srcs = [dc.weight, dbn.weight, dbn.bias, dbn.running_mean, dbn.running_var,
+                rbn.weight, rbn.bias, rbn.running_mean, rbn.running_var, fin.weight, fin.bias]
+
+        def build():
+            ds, db = fold_bn(dbn)
+            _, rb = fold_bn(rbn)
+            wf, t27 = E.fold_pointwise_into_deconv(fin.weight, fin.bias, dc.weight, ds, db + rb)
+            return pack_deconv_weight_bf16s(pack_conv_weight(wf, transposed=True), _deconv_nterms()), t27
+        return _cache(self).get("u5fold/" + E.CONV_ENGINE + "/%d" % _deconv_nterms(), srcs, build)
+
+    def _up5_folded(self, y, skip):
+        """relu(bn(conv5(final1x1(y))) + bn(redir2(skip))) in ONE launch, `y` the attention block's output before final1x1."""
+        wd, _, _, _, wrs = self._up_params("u5", self.conv5, self.redir2)
+        wfs, t27 = self._up5_folded_params()
+        return E.deconv3d_bf16s_shift27_hip(y, wfs, wd.shape[2], t27, True, _deconv_nterms(), skip, wrs)
 
     def forward(self, x):
         x = dfr.real(x)
@@ -384,9 +423,18 @@ class hourglass(nn.Module):
         at("c3")
         c4 = run_convbn(self, "c4", self.conv4[0][0], self.conv4[0][1], c3, relu=True)
         at("c4")
-        c4 = self.attention_block(c4)
-        at("att")
-        c5 = self._up("u5", self.conv5, self.redir2, c4, c2)
+        ab = self.attention_block
+        # ATTN_FOLD: final1x1 is a linear map in front of a linear layer with constant weights -- composed into conv5's packed
+        # weights once per weight version instead of run per call (only where conv5 runs on the split engine's kernel)
+        if (E.ATTN_FOLD and isinstance(ab, attention_block) and ab.folds_final(c4)
+                and self._up_takes_split_engine("u5", self.conv5, self.redir2, c4)):
+            y = ab(c4, final=False)
+            at("att")
+            c5 = self._up5_folded(y, c2)
+        else:
+            c4 = ab(c4)
+            at("att")
+            c5 = self._up("u5", self.conv5, self.redir2, c4, c2)
         at("u5")
         return self._up("u6", self.conv6, self.redir1, c5, x)
 

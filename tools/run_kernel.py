@@ -2,7 +2,9 @@
 """Runs ONE kernel of the path back to back (live shapes of the 1024 x 1024 / maxdisp 128 pair) so that rocprofv3 kernel-trace /
 PMC passes see nothing else, and prints its time and algorithmic-byte rate.
 usage: run_kernel.py <kernel> [batch] [iters]        kernels: gwc gwc_fused patch head head_att classif classif_cl classif_plain classif_att head_cl conv_s1_cl conv_mid conv_low conv_mid_att conv_low_att attn attn_att warp ssr ssr2048 strength topk
-                                                               catt8 catt4 upsoft stem_left stem_left_mfma stem_left2048 stem_left_mfma2048 stem stem_gather stem_gather_smooth conv_s1 conv_s2 conv_s2_att deconv deconv5 deconv_att6 deconv_att5"""
+                                                               catt8 catt4 upsoft stem_left stem_left_mfma stem_left2048 stem_left_mfma2048 stem stem_gather stem_gather_smooth conv_s1 conv_s2 conv_s2_att deconv deconv5 deconv_att6 deconv_att5
+                                                               attn_core attn_att_core (the block without final1x1; SS_ATTENTION=split|proj picks the form, for attn / attn_att too)
+                                                               deconv5_two deconv_att5_two deconv5_fold deconv_att5_fold (final1x1 + conv5 as two launches / folded into one)"""
 import os
 import sys
 import time
@@ -83,11 +85,11 @@ elif name in ("stem_left", "stem_left_mfma", "stem_left2048", "stem_left_mfma204
     cl, att = R(B, 32, hq, hq), torch.rand(B, 1, 24, hq, hq, device=dev)
     fn = lambda: M.stem_broadcast_half(stem, cl, att)                          # noqa: E731
     nbytes = 4.0 * B * (32 + 24 + 32 * 24) * hq * hq
-elif name in ("attn", "attn_att"):       # attention_block of hourglass2 ([128,6,64,64], windows 6x4x4) / of the attention-branch hourglass ([128,8,32,32], 4x4x4)
-    blk, d, hw = ((6, 4, 4), 6, 64) if name == "attn" else ((4, 4, 4), 8, 32)
+elif name in ("attn", "attn_att", "attn_core", "attn_att_core"):       # attention_block of hourglass2 ([128,6,64,64], windows 6x4x4) / of the attention-branch hourglass ([128,8,32,32], 4x4x4)
+    blk, d, hw = ((6, 4, 4), 6, 64) if name in ("attn", "attn_core") else ((4, 4, 4), 8, 32)
     ab = M.attention_block(128, 16, blk).to(dev).eval()
     x = R(B, 128, d, hw, hw)
-    fn = lambda: ab(x)                                                         # noqa: E731
+    fn = (lambda: ab(x, final=False)) if name.endswith("_core") else (lambda: ab(x))       # noqa: E731
     nbytes = 4.0 * B * 2 * 128 * d * hw * hw
 elif name in ("conv_mid", "conv_low", "conv_mid_att", "conv_low_att"):   # hourglass2.conv2: 64 -> 64 at [12,128,128]; conv4: 128 -> 128 at [6,64,64]; hourglass_att's: [16,64,64], [8,32,32]
     c, d, hw = {"conv_mid": (64, 12, 128), "conv_low": (128, 6, 64), "conv_mid_att": (64, 16, 64), "conv_low_att": (128, 8, 32)}[name]
@@ -142,7 +144,9 @@ elif name == "conv_s2_att":      # hourglass_att.conv3: 64 -> 128 stride 2 on [1
     sc, sh = torch.rand(128, device=dev) + 0.5, R(128) * 0.1
     fn = lambda: M.conv3d_bf16s_hip(x, ws, 128, sc, sh, True, 19, stride=2)       # noqa: E731
     nbytes = 4.0 * B * (64 * 16 * 64 * 64 + 128 * 8 * 32 * 32)
-elif name in ("deconv5", "deconv_att6", "deconv_att5"):     # the other three transposed convs of the step
+elif name in ("deconv5", "deconv_att6", "deconv_att5", "deconv5_two", "deconv_att5_two", "deconv5_fold", "deconv_att5_fold"):     # the other three transposed convs of the step
+    form = name.rsplit("_", 1)[1] if name.endswith(("_two", "_fold")) else ""
+    name = name[:-len(form) - 1] if form else name
     hg = (M.hourglass2(32) if name == "deconv5" else M.hourglass(32)).to(dev).eval()
     if name == "deconv5":        # hourglass2.conv5: 128 -> 64 from [6,64,64] + redir2 of the 64-channel [12,128,128] volume
         xin, xskip, args = torch.relu(R(B, 128, 6, 64, 64)), torch.relu(R(B, 64, 12, 128, 128)), ("u5", hg.conv5, hg.redir2)
@@ -151,6 +155,11 @@ elif name in ("deconv5", "deconv_att6", "deconv_att5"):     # the other three tr
     else:                        # hourglass_att.conv5: 128 -> 64 from [8,32,32] + redir2 of [64,16,64,64]
         xin, xskip, args = torch.relu(R(B, 128, 8, 32, 32)), torch.relu(R(B, 64, 16, 64, 64)), ("u5", hg.conv5, hg.redir2)
     fn = lambda: hg._up(*args, xin, xskip)                                     # noqa: E731
+    if form == "fold":           # attention_block.final1x1 composed into conv5's packed weights (SS_ATTN_FOLD): one launch
+        fn = lambda: hg._up5_folded(xin, xskip)                                # noqa: E731
+    elif form == "two":          # ... and what it replaces: the final1x1 launch, then conv5
+        _, _, wo, bo, _ = hg.attention_block._params_split()
+        fn = lambda: hg._up(*args, M.conv3d_pointwise_bf16s_hip(xin, wo, 128, None, bo, False, M._aux_nterms()), xskip)    # noqa: E731
     nbytes = 4.0 * B * (xin[0].numel() + 2 * xskip[0].numel())
 elif name in ("conv_s2", "conv_s1", "deconv"):
     if name == "deconv":            # hourglass2.conv6: 64 -> 32 to [24,256,256] with the 1x1x1 skip projection of a 32-channel volume
@@ -234,5 +243,5 @@ with torch.no_grad():
     e1.record()
     torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / iters
-print(f"{name} B={B}: {ms * 1e3:.1f} us/launch, {nbytes / 1e6:.1f} MB algorithmic, {nbytes / ms / 1e6:.0f} GB/s = "
+print(f"{sys.argv[1]} B={B}: {ms * 1e3:.1f} us/launch, {nbytes / 1e6:.1f} MB algorithmic, {nbytes / ms / 1e6:.0f} GB/s = "
       f"{100 * nbytes / ms / 1e6 / 8000:.1f} % of 8 TB/s")
