@@ -126,8 +126,9 @@ int ss_concat_sampled_fwd(const float* left, const float* right, const float* di
  * F.grid_sample, zeros padding, align_corners=True as the forward) and grad_att [B,nd,H,W] (= sum_c grad . the ungated volume); any of
  * the three may be NULL; att may be NULL when grad_att is.  The candidates `disp` are constants (the indices of
  * models/SemStereo.py:299-305): no gradient.  `margin`: a bound on |disp| the caller expects (a performance hint: taps further away are
- * added one atomic at a time instead of through the LDS windows; any value gives the same result).  W % 64 == 0 (every
- * quarter-resolution width of the path), else SS_ERR_UNSUPPORTED: the caller composes ss_warp_sampled_bwd with its own cat / multiply. */
+ * added one atomic at a time instead of through the LDS windows; any value gives the same result).  Any width: a
+ * workgroup owns 64 columns of one row, the last block of a row may be partial (W % 64 == 0: whole blocks, the launch of the path's
+ * own quarter-resolution widths).  SS_ERR_UNSUPPORTED beyond 2^31 - 1 such blocks (B * H * ceil(W / 64)). */
 int ss_concat_sampled_bwd(const float* grad_out, const float* left, const float* right, const float* disp, const float* att,
                           float* grad_left, float* grad_right, float* grad_att, int B, int C, int H, int W, int nd, int margin,
                           ss_stream_t stream);

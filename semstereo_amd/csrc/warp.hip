@@ -663,6 +663,10 @@ extern "C" int ss_concat_sampled_fwd(const float* left, const float* right, cons
 //   grad_right[c]  <- att[j] * w_tap * gR[c,j] at the four taps           (the two row windows of warp_bwd_blocks_kernel)
 // with gL / gR the two halves of the volume's gradient.  `margin`: the |disparity| the windows cover (a hint: taps beyond go to
 // memory one atomic at a time, still right).
+// The 64 pixels of a workgroup lie in one row: blockIdx.x runs over (b, h, block of 64 columns), lane l owns column x0 + l.  RAGGED
+// (W % 64 != 0): the lanes of a row's last block whose column is >= W are inactive -- they read the row's last pixel (an address
+// inside the tensors) and have every value zeroed, add nothing to the windows, to memory or to the partial sums, store nothing, and
+// keep every barrier.  With RAGGED false every lane is active at compile time: the kernel of whole-block rows, unchanged.
 #ifndef SS_CSB_CH
 #define SS_CSB_CH 4
 #endif
@@ -673,6 +677,7 @@ extern "C" int ss_concat_sampled_fwd(const float* left, const float* right, cons
 #define SS_CSB_JU 2
 #endif
 constexpr int CSB_NW = SS_CSB_NW, CSB_CH = SS_CSB_CH, CSB_JU = SS_CSB_JU;
+template <bool RAGGED>
 __global__ __launch_bounds__(64 * CSB_NW) void concat_sampled_bwd_kernel(const float* __restrict__ gvol, const float* __restrict__ left,
                                                                          const float* __restrict__ right, const float* __restrict__ disp,
                                                                          const float* __restrict__ att, float* __restrict__ g_left,
@@ -687,9 +692,20 @@ __global__ __launch_bounds__(64 * CSB_NW) void concat_sampled_bwd_kernel(const f
     float* red = csb_lds + (size_t)2 * CSB_NW * (2 * CSB_CH * rs) + (size_t)CSB_NW * (2 * rs);
     const int rb = 64 + 2 * margin + 2;                       // live slots of a window
     const long long plane = (long long)H * W;
-    const long long i = (long long)blockIdx.x * 64 + lane;    // over B * H * W (whole blocks: W % 64 == 0)
-    const int w = (int)(i % W), h = (int)((i / W) % H);
-    const long long b = i / plane, pix = (long long)h * W + w;
+    // i: the lane's pixel over B * H * W (an inactive lane: the last pixel of its row); x0: the block's first column
+    long long i = (long long)blockIdx.x * 64 + lane;          // whole blocks (W % 64 == 0)
+    int x0 = 0, w;
+    if constexpr (RAGGED) {
+        const int nxb = (W + 63) >> 6;                        // blockIdx.x over B * H * nxb: (b, h, x0 = 64 * xblock)
+        x0 = (int)(blockIdx.x % (unsigned)nxb) * 64;
+        w = x0 + lane;
+        i = (long long)(blockIdx.x / (unsigned)nxb) * W + min(w, W - 1);
+    } else {
+        w = (int)(i % W);
+    }
+    const bool act = !RAGGED || w < W;                        // (x0 < W: lane 0 of every block is active)
+    const int h = (int)((i / W) % H);
+    const long long b = i / plane, pix = (long long)h * W + (RAGGED ? min(w, W - 1) : w);
     const int c0 = (blockIdx.y * CSB_NW + wave) * CSB_CH;
     const int nlive = max(0, min(CSB_CH, C - c0));            // (wave-uniform; 0: the wave only keeps the barriers)
     for (int k = lane; k < 2 * CSB_CH * rs; k += 64) ss::lds_put(&rows[k], 0.f);
@@ -697,13 +713,13 @@ __global__ __launch_bounds__(64 * CSB_NW) void concat_sampled_bwd_kernel(const f
     const float* gr_p = gvol + (b * 2 * C + C + c0) * nd * plane;     // ... of the warped half
     const float* rp = right + (b * C + c0) * plane;
     float* grp = g_right ? g_right + (b * C + c0) * plane : nullptr;
-    const int xb = (int)(((long long)blockIdx.x * 64) % W) - margin;
+    const int xb = (RAGGED ? x0 : (int)(((long long)blockIdx.x * 64) % W)) - margin;
     const int yn = (int)floorf(ss::mul_rn(((float)h / half_h - 1.0f) + 1.0f, half_h));
     const int other = (yn == h) ? h + 1 : yn;
     float cl[CSB_CH], gcl[CSB_CH];
 #pragma unroll
     for (int n = 0; n < CSB_CH; ++n) {
-        cl[n] = (n < nlive) ? left[(b * C + c0 + n) * plane + pix] : 0.f;
+        cl[n] = (n < nlive && act) ? left[(b * C + c0 + n) * plane + pix] : 0.f;
         gcl[n] = 0.f;
     }
     // the same two windows of `right` itself (zeros outside the image): the forward's warp(right)[c, j], which grad_att needs, is four
@@ -731,8 +747,8 @@ __global__ __launch_bounds__(64 * CSB_NW) void concat_sampled_bwd_kernel(const f
             av[u] = att ? att[(b * nd + j) * plane + pix] : 1.f;
 #pragma unroll
             for (int n = 0; n < CSB_CH; ++n) {
-                gL[u][n] = (n < nlive) ? gl_p[((long long)n * nd + j) * plane + pix] : 0.f;
-                gR[u][n] = (n < nlive) ? gr_p[((long long)n * nd + j) * plane + pix] : 0.f;
+                gL[u][n] = (n < nlive && act) ? gl_p[((long long)n * nd + j) * plane + pix] : 0.f;
+                gR[u][n] = (n < nlive && act) ? gr_p[((long long)n * nd + j) * plane + pix] : 0.f;
             }
         }
 #pragma unroll
@@ -762,14 +778,14 @@ __global__ __launch_bounds__(64 * CSB_NW) void concat_sampled_bwd_kernel(const f
 #pragma unroll
             for (int n = 0; n < CSB_CH; ++n) {
                 gcl[n] = fmaf(a, gL[u][n], gcl[n]);
-                const float val = (n < nlive) ? wval(n) : 0.f;                          // the forward's warp(right)[c, j]
+                const float val = (n < nlive && act) ? wval(n) : 0.f;                   // the forward's warp(right)[c, j]
                 s = fmaf(gL[u][n], cl[n], s);
                 s = fmaf(gR[u][n], val, s);
             }
-            part[u] = s;
+            part[u] = act ? s : 0.f;
             if (grp != nullptr) {
                 auto add = [&](int o, int row, float wt) {
-                    const bool any = o >= 0 && wt != 0.f;
+                    const bool any = act && o >= 0 && wt != 0.f;
                     if (__builtin_amdgcn_ballot_w64(any) == 0) return;
                     const int r = (row == h) ? 0 : 1;
                     const unsigned k = (unsigned)(o - row * W - xb);
@@ -798,6 +814,7 @@ __global__ __launch_bounds__(64 * CSB_NW) void concat_sampled_bwd_kernel(const f
 #pragma unroll
                     for (int wv = 0; wv < CSB_NW; ++wv) t += red[((par * CSB_NW + wv) * CSB_JU + u) * 64 + lane];
                     float* dst = g_att + (b * nd + j0 + u) * plane + pix;
+                    if (!act) continue;
                     if (att_atomic) unsafeAtomicAdd(dst, t); else *dst = t;
                 }
             }
@@ -806,7 +823,7 @@ __global__ __launch_bounds__(64 * CSB_NW) void concat_sampled_bwd_kernel(const f
     if (g_left != nullptr) {
 #pragma unroll
         for (int n = 0; n < CSB_CH; ++n)
-            if (n < nlive) g_left[(b * C + c0 + n) * plane + pix] = gcl[n];
+            if (n < nlive && act) g_left[(b * C + c0 + n) * plane + pix] = gcl[n];
     }
     if (grp == nullptr) return;
     __builtin_amdgcn_wave_barrier();
@@ -831,7 +848,8 @@ extern "C" int ss_concat_sampled_bwd(const float* grad_out, const float* left, c
                                      ss_stream_t stream) {
     SS_REQUIRE(grad_out && left && right && disp && B > 0 && C > 0 && H > 0 && W > 0 && nd > 0 && margin >= 0);
     SS_REQUIRE(grad_att == nullptr || att != nullptr);
-    if (W % 64 != 0 || (long long)B * H * W / 64 > 0x7fffffffLL || ss::ceil_div(C, CSB_NW * CSB_CH) > 65535) return SS_ERR_UNSUPPORTED;
+    const long long blocks = (long long)B * H * ss::ceil_div(W, 64);          // a workgroup: 64 columns of one row, any W
+    if (blocks > 0x7fffffffLL || ss::ceil_div(C, CSB_NW * CSB_CH) > 65535) return SS_ERR_UNSUPPORTED;
     hipStream_t st = ss::as_stream(stream);
     const long long plane = (long long)H * W;
     margin = std::min(margin, 96);
@@ -842,9 +860,10 @@ extern "C" int ss_concat_sampled_bwd(const float* grad_out, const float* left, c
     if (grad_right && hipMemsetAsync(grad_right, 0, (size_t)B * C * plane * sizeof(float), st) != hipSuccess) return SS_ERR_LAUNCH;
     if (grad_att && gy > 1 && hipMemsetAsync(grad_att, 0, (size_t)B * nd * plane * sizeof(float), st) != hipSuccess) return SS_ERR_LAUNCH;
     const float half_w = (float)((W - 1.0) / 2.0), half_h = (float)((H - 1.0) / 2.0);
-    if (lds > 64 * 1024 && ss::ensure_dynamic_lds(reinterpret_cast<const void*>(concat_sampled_bwd_kernel), (int)lds) != SS_OK) return SS_ERR_LAUNCH;
-    hipLaunchKernelGGL(concat_sampled_bwd_kernel, dim3((unsigned)((long long)B * plane / 64), gy), dim3(64 * CSB_NW), lds, st, grad_out, left,
-                       right, disp, att, grad_left, grad_right, grad_att, C, H, W, nd, half_w, half_h, margin, rs, gy > 1 ? 1 : 0);
+    const auto kernel = (W % 64 != 0) ? concat_sampled_bwd_kernel<true> : concat_sampled_bwd_kernel<false>;
+    if (lds > 64 * 1024 && ss::ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)lds) != SS_OK) return SS_ERR_LAUNCH;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks, gy), dim3(64 * CSB_NW), lds, st, grad_out, left, right, disp, att, grad_left,
+                       grad_right, grad_att, C, H, W, nd, half_w, half_h, margin, rs, gy > 1 ? 1 : 0);
     return ss::check_launch();
 }
 

@@ -219,8 +219,9 @@ def fused_training_forward(self, left, right, reference_forward=None):
     """The training counterpart of `fused_inference_forward`: models/SemStereo.py:246-346 for train() calls and for eval() calls
     under autograd (frozen statistics) -- the same sub-module calls in the same order as the reference's forward() around
     `segment.run_segment`, which under autograd runs :279-310 as `train.attention_tail` and :316-318 as `train.concat_volume_sampled`
-    (where either declines -- a quarter-resolution width that is no multiple of 64 -- the statements run, counted in
-    PATH_COUNTS["train_tail_statements"] / ["train_concat_statements"]).  Every sub-module is called once per view as the reference
+    (where either declines the statements run, counted in PATH_COUNTS["train_tail_statements"] / ["train_concat_statements"]: by
+    default the concat volume declines a quarter-resolution width that is no multiple of 64; with SS_TRAIN_CONCAT_ANY_WIDTH=1,
+    `train.CONCAT_VOLUME_ANY_WIDTH`, it takes every width).  Every sub-module is called once per view as the reference
     calls it -- no pair launch merges the two views' batch statistics, and `ssr_upsample` runs on `pred_att` (:311) and then on `pred`
     (:324) -- so every BatchNorm sees the reference's calls in the reference's order.  Returns what the reference returns:
     `[pred_up*4, pred.squeeze(1)*4, pred_att_up*4, pred_att*4], pred_label, pred_label_r` in train() (`[pred_att_up*4, pred_att*4], ...`

@@ -306,7 +306,7 @@ class HotSegment(nn.Module):
                 # training (r06): :316-318 as one launch each way instead of a warp, a cat and a multiply and their three backwards
                 volume = T.concat_volume_sampled(cl, cr, samples, att_topk, margin=max(self.maxdisp // 4, 1))
             else:
-                if torch.is_grad_enabled():     # (the one-launch form declined, e.g. W/4 no multiple of 64: counted)
+                if torch.is_grad_enabled():     # (the one-launch form declined, e.g. W/4 no multiple of 64 without SS_TRAIN_CONCAT_ANY_WIDTH=1: counted)
                     M.PATH_COUNTS["train_concat_statements"] = M.PATH_COUNTS.get("train_concat_statements", 0) + 1
                 right_w, left_b = ops.SpatialTransformer_grid(cl, cr, samples)                 # :241-242 (concat_volume_generator)
                 volume = torch.cat((left_b, right_w), dim=1)                                   # :243

@@ -537,6 +537,9 @@ def attention_tail(cost_att, left, right, gamma, beta, rng, H, W, k):
 # ---- the sparse concat volume (models/SemStereo.py:316-318) -------------------------------------------------------------------------
 
 CONCAT_VOLUME_FUSED = os.environ.get("SS_TRAIN_CONCAT_FUSED", "1") != "0"
+#: 1: the one-launch form at every width (rows of partial 64-pixel blocks too), not only where W % 64 == 0.  Off by default:
+#: tests/test_train_route_gpu.py pins the statements at 128 x 160.  Read at each call of concat_volume_applies.
+CONCAT_VOLUME_ANY_WIDTH = os.environ.get("SS_TRAIN_CONCAT_ANY_WIDTH", "0") == "1"
 
 
 class _ConcatVolumeSampled(torch.autograd.Function):
@@ -572,16 +575,20 @@ class _ConcatVolumeSampled(torch.autograd.Function):
 
 
 def concat_volume_applies(left, right, samples, att):
-    """The one-launch form under autograd: fp32 HIP maps whose rows are whole 64-pixel blocks (every quarter-resolution width of the
-    path), candidates that need no gradient, one gate per (candidate, pixel)."""
+    """The one-launch form under autograd: fp32 HIP maps, candidates that need no gradient, one gate per (candidate, pixel), and rows
+    of whole 64-pixel blocks (every quarter-resolution width of the path) -- or, with CONCAT_VOLUME_ANY_WIDTH
+    (SS_TRAIN_CONCAT_ANY_WIDTH=1, off by default, read here at each call), rows of any width: ss_concat_sampled_bwd takes a partial
+    last block per row."""
     if not (CONCAT_VOLUME_FUSED and _on(left) and _on(right) and _on(samples) and _on(att)):
         return False
     if samples.requires_grad or left.dim() != 4 or left.shape != right.shape or samples.dim() != 4:
         return False
     B, C, H, W = right.shape
     nd = samples.shape[1]
-    return (W % 64 == 0 and tuple(samples.shape) == (B, nd, H, W) and att.numel() == B * nd * H * W and att.shape[0] == B
-            and tuple(att.shape[-3:]) == (nd, H, W) and (B * H * W) // 64 < 2 ** 31)
+    if W % 64 != 0 and not CONCAT_VOLUME_ANY_WIDTH:
+        return False
+    return (tuple(samples.shape) == (B, nd, H, W) and att.numel() == B * nd * H * W and att.shape[0] == B
+            and tuple(att.shape[-3:]) == (nd, H, W) and B * H * ((W + 63) // 64) < 2 ** 31)
 
 
 def concat_volume_sampled(left, right, samples, att, margin=64):
