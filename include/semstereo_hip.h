@@ -773,6 +773,27 @@ int ss_disparity_metrics_fwd(const float* est0, const float* est1, const float* 
 int ss_seg_confusion_fwd(const float* logits, const void* labels, int label_dtype, int B, int num_classes, int H, int W,
                          long long label_row_stride, long long label_image_stride, long long* joint, int accumulate, void* workspace,
                          long long workspace_bytes, ss_stream_t stream);
+/* ---- the joint stereo-semantic record (disparity error per semantic class, mIoU-3), csrc/joint_metrics.hip ----
+ * One more streaming reduction of the same kind, over the tensors the two calls above read, once: n_est <= 4 estimates [B,H,W] against
+ * gt; the mask (bool) or, with mask NULL, lo <= gt < hi; labels decoded exactly as in ss_seg_confusion_fwd (dtype codes, strides, class
+ * g in [0, 6) or 6 = outside); logits [B,6,H,W] with p = their first maximum, or NULL: the three joint tables are not produced and
+ * may be NULL.  E = |gt - est| in fp32; d1 = E > 3 & E / |gt| > 0.05; thr_k = E > t_k, k < n_thr <= 4; good = in the mask & E < tau
+ * (E == tau and a NaN E are not good).  All outputs are PER IMAGE, so the caller applies the skip rule and accumulates on the device:
+ *   image      [B][2] int64             n_mask, n_pos (= #(gt > 0))
+ *   cls_sel    [B][7] int64             pixels in the mask, per class
+ *   cls_counts [n_est][B][7][5] int64   n_d1, n_thr[4] of the pixels in the mask, per class
+ *   cls_sums   [n_est][B][7] doubles    sum of E over them (fp32 values added in double from the thread on)
+ *   joint_all, joint_out [B][7][6] int64   every pixel / the pixels outside the mask, by (g, p)
+ *   joint_good [n_est][B][7][6] int64   the good pixels (bad = all - out - good)
+ * Integer counts are exact; one partial per workgroup, a second launch adds them in a fixed order; no floating-point atomics.
+ * workspace: ss_joint_metrics_scratch(n_est, B) bytes.  num_classes != 6, more than 1024 images, H W >= 2^31 - 1: -2. */
+int ss_joint_metrics_scratch(int n_est, int B, long long* bytes);
+int ss_joint_metrics_fwd(const float* est0, const float* est1, const float* est2, const float* est3, const float* gt,
+                         const unsigned char* mask, const float* logits, const void* labels, int label_dtype, long long label_row_stride,
+                         long long label_image_stride, int n_est, int B, int num_classes, int H, int W, float lo, float hi, float t0,
+                         float t1, float t2, float t3, int n_thr, float tau, long long* image, long long* cls_sel, long long* cls_counts,
+                         double* cls_sums, long long* joint_all, long long* joint_out, long long* joint_good, void* workspace,
+                         long long workspace_bytes, ss_stream_t stream);
 /* ---- the evaluation step's image outputs (main_us3d.py:252, :265-268; main_whu.py:242, :250-251), csrc/vis.hip ----
  * Streaming passes without atomics: a lane takes 4 consecutive pixels of a row (16-byte accesses where the address allows), results are
  * planar [B,3,H,W], element offsets are 64-bit, every division is the IEEE one.  Nothing comes back to the host.  A map of 2^31 or more

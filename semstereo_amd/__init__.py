@@ -6,6 +6,7 @@
   install   install(model_module) / accelerate(model): drop-in into the reference's own model
   losses    the training objective under the reference's names (models/loss.py), install_losses(script_module)
   metrics   the evaluation step's metrics under the reference's names (utils/metrics.py), install_metrics(script_module)
+  joint_metrics  disparity error per semantic class and mIoU-3 from one pass: joint_metrics, JointMetric, eval_metrics_joint
   visualization  the evaluation step's image outputs under the reference's names (utils/visualization.py, utils/mask_vis.py),
             install_visualization(script_module)
   data      the datasets' sample preparation on the device (datasets/us3d_.py, datasets/whu_dataset.py): normalised views, ground-truth
@@ -15,10 +16,11 @@
 The compute lives in csrc/libsemstereo_hip.so behind the C ABI of include/semstereo_hip.h.
 Nothing here falls back to the CPU or to the test oracle.
 """
-from . import _lib, data, dist, engine, losses, metrics, modules, ops, ops_unsigned, segment, train_layers, visualization  # noqa: F401
+from . import _lib, data, dist, engine, joint_metrics, losses, metrics, modules, ops, ops_unsigned, segment, train_layers, visualization  # noqa: F401
 from .install import accelerate, install, install_losses, install_metrics, install_visualization, restore_forward, uninstall  # noqa: F401
 from .losses import LRSC_loss, model_label_loss, model_loss_test, model_loss_train, train_objective  # noqa: F401
 from .metrics import EvalAverager, SegmentationMetric, disparity_metrics, eval_metrics  # noqa: F401
+from .joint_metrics import JointMetric, eval_metrics_joint  # noqa: F401  (the record itself: joint_metrics.joint_metrics)
 from .visualization import disp_error_image_func, eval_images, feature_vis, label_vis, normalize_image  # noqa: F401
 from .data import DeviceLoader, RawStereoDataset, image_gradients, nearest_pyramid, normalize_views, prepare_sample  # noqa: F401
 from .segment import GraphedSegment, HotSegment, PairPipeline  # noqa: F401

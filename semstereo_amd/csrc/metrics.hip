@@ -6,29 +6,17 @@
 // partials in a fixed order: no floating-point atomics, two calls on the same inputs return the same bits.  Nothing here allocates,
 // copies or synchronises, and nothing comes back to the host.
 #include "common.h"
+#include "metrics_decode.h"
 
 namespace {
 
-constexpr int NC = 6;          // channels of the logits (the reference's US3D setting, main_us3d.py: nums = 6)
-constexpr int NBIN = (NC + 1) * NC;      // joint histogram: label 0..5 and "outside" x prediction 0..5
+using namespace ss::metrics;   // NC, NBIN, LT_*, label_row, argmax6, aligned16, wave_sum: shared with joint_metrics.hip
+
 constexpr int BLOCK = 256;
 constexpr int GM = 1024;       // workgroups of the disparity metrics, all images together
 constexpr int GC = 1024;       // workgroups of the confusion matrix
 constexpr int NEST = 4, NTHR = 4;
 constexpr int NCNT = 8;        // record of counts per (estimate, image): n_sel, n_mask, n_pos, n_d1, n_thr[4]
-
-__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 // ---------------------------------------------------------------- EPE / D1 / Thres (utils/metrics.py:16-59, :63-89)
 struct MetricArgs {
@@ -208,8 +196,6 @@ __global__ __launch_bounds__(BLOCK) void disp_metrics_finish_k(MetricArgs a, int
 }
 
 // ---------------------------------------------------------------- confusion matrix (utils/metrics.py:143-168)
-enum { LT_I64 = 0, LT_U8 = 1, LT_F32 = 2 };
-
 struct ConfArgs {
     const float* z;            // logits [B,NC,H,W]
     const void* y;             // labels, at least [B,H,W]: pixel (b, h, x) at b * y_img + h * y_row + x
@@ -219,35 +205,6 @@ struct ConfArgs {
     long long* out;            // [NC + 1][NC]
     int accumulate;
 };
-
-// the class of a label in [0, NC), or NC for "outside": never an index out of bounds.  Float labels truncate toward zero as the
-// reference's np.asarray(..., dtype=int) does; NaN is outside.
-template <int LT>
-__device__ __forceinline__ int label_row(const void* y, long long i) {
-    if (LT == LT_I64) {
-        const long long v = reinterpret_cast<const long long*>(y)[i];
-        return (v < 0 || v >= NC) ? NC : (int)v;
-    }
-    if (LT == LT_U8) {
-        const int v = reinterpret_cast<const unsigned char*>(y)[i];
-        return v >= NC ? NC : v;
-    }
-    const float f = reinterpret_cast<const float*>(y)[i];
-    return (f > -1.f && f < (float)NC) ? (int)f : NC;
-}
-
-// np.argmax: the lowest index among equal maxima, and a NaN counts as the maximum (the first one wins)
-__device__ __forceinline__ int argmax6(const float (&z)[NC]) {
-    float best = z[0];
-    int idx = 0;
-#pragma unroll
-    for (int k = 1; k < NC; ++k) {
-        const bool take = best == best && (z[k] > best || z[k] != z[k]);
-        best = take ? z[k] : best;
-        idx = take ? k : idx;
-    }
-    return idx;
-}
 
 // How a wave counts 42 bins: every lane owns a column of the workgroup's histogram in LDS, hist[bin][lane], and adds 1 to it with a
 // ds_add_u32 that returns nothing.  The 64 lanes of one instruction hit 64 different banks whatever their bins are, so the cost does not
