@@ -120,6 +120,12 @@ __device__ __forceinline__ Taps4 bilinear_taps(float disp, int h, int w, int H, 
     return t;
 }
 
+// 1 - sigmoid(u) = sigmoid(-u), formed on its own: as 1.0f - gate it keeps an absolute error of 6e-8 where the gate is near one (beta +
+// gamma * var = 7 leaves 1e-3: six parts in 1e5 of the sigmoid's derivative), and grad_gamma, a sum over all pixels that cancels to a few
+// per cent of its terms, missed its bound on tests/bwd_path_cases.py's `ragged` (6.3e-5 of the float64 value; fp32 autograd of
+// torch.sigmoid does the same: 6.6e-5).
+__device__ __forceinline__ float one_minus_sigmoid(float u) { return 1.0f / (1.0f + expf(u)); }
+
 // A workgroup = 64 pixels (lanes along x) x NW waves that split the channels (wave w owns channels w, w + NW, ...).  Pass 1
 // recomputes corr[t] = mean_c left * warp_t(right) -- each wave its channels, summed through LDS in a fixed order -- and every wave
 // redoes the small softmax backward for its lanes' pixels; pass 2 walks the wave's channels again for the feature gradients.  g_left is
@@ -208,7 +214,7 @@ __global__ __launch_bounds__(64 * SSB_NW, 4) void sample_strength_bwd_kernel(con
         const float dz = z[t] * (gs[t] - dot);
         dcorr[t] = dz * gate[t] / (float)C;
         if (wave == 0 && active) {                           // (wave-uniform) the per-pixel scalars: once per pixel
-            const float dv = dz * corr[t] * gate[t] * (1.0f - gate[t]);
+            const float dv = dz * corr[t] * gate[t] * one_minus_sigmoid(bt + g * var[nbs[t]]);
             dbeta += dv;
             dgamma += dv * var[nbs[t]];
             if (g_var) unsafeAtomicAdd(&g_var[nbs[t]], dv * g);
@@ -357,7 +363,7 @@ __global__ __launch_bounds__(64 * SSB_NW) void ssb_dcorr_kernel(const float* __r
         const float dz = z[t] * (gs[t] - dot);
         if (active) {
             dcorr_out[(b * 5 + t) * plane + pix] = dz * gate[t] / (float)C;
-            const float dv = dz * corr[t] * gate[t] * (1.0f - gate[t]);
+            const float dv = dz * corr[t] * gate[t] * one_minus_sigmoid(bt + g * var[nbs[t]]);
             dbeta += dv;
             dgamma += dv * var[nbs[t]];
             if (g_var) unsafeAtomicAdd(&g_var[nbs[t]], dv * g);

@@ -306,7 +306,8 @@ __global__ void gwc_volume_bwd_kernel(const float* __restrict__ gout, const floa
 // ... row by row (r06; W <= GB_WMAX, D <= GB_DMAX, Cg <= 8: every live shape): a workgroup owns one image row of one (batch element,
 // group) and stages that row of the gradient's D planes and of the group's Cg channels of both maps in LDS once -- the thread-per-element
 // form above fetches every gradient value Cg times and every feature value 2 D times through the caches (442 us at batch 4 of the
-// 1024^2 training shape for 200 MB of tensors).  Same sums in the same order as above (d ascending), so the results are identical.
+// 1024^2 training shape for 200 MB of tensors).  Same sums in the same order as above (d ascending), so the results are identical
+// (tests/test_bwd_paths_gpu.py::test_gwc_volume_backward_kernels_form_the_same_sums: bit for bit, through a power-of-two widening).
 constexpr int GB_WMAX = 512, GB_DMAX = 48;
 __global__ __launch_bounds__(256) void gwc_volume_bwd_rows_kernel(const float* __restrict__ gout, const float* __restrict__ ref,
                                                                    const float* __restrict__ tgt, float* __restrict__ gref,

@@ -48,7 +48,9 @@ STEP_SEAMS = frozenset({
 })
 
 #: bound per (seam, part) -- the bound the seam's small-shape test asserts (tests/test_parity_gpu.py), as max|err| / max|ref|.  Where that
-#: test asserts atol + rtol * max|ref| on O(1) data, the bound is atol + rtol.
+#: test asserts atol + rtol * max|ref| on O(1) data, the bound is atol + rtol.  tests/test_bwd_paths_gpu.py holds _UpsampleSoftmaxRegression,
+#: _SampleStrength (both forms of its backward), _TopkCandidates, _GwcVolume and _GroupNormalise to these same entries on every
+#: shape-dependent path of their backward kernels (row buffers, the thread-per-element volume kernel, zero groups, NULL gradients).
 BOUNDS = {
     "train_layers._conv_k3_forward": {"fwd": 2e-6},                          # test_conv3d_training_forward_dgrad_wgrad_in_hip
     "train_layers._deconv_k3_forward": {"fwd": 2e-6},                        # ... and test_deconv3d_training_...
