@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/semstereo_hip.h"
 
@@ -63,6 +64,16 @@ inline int range_halo(int dmin, int ndisp) {
     return m <= 0 ? 0 : (m + 3) / 4 * 4;
 }
 __host__ __device__ inline long long ceil_div_ll(long long a, long long b) { return (a + b - 1) / b; }
+
+// Runtime value -> compile-time constant: fn(std::true_type / std::false_type), fn(std::integral_constant<int, V>) for the V among
+// Vs that equals v (none: SS_ERR_INVALID).  The launchers pick a kernel instantiation with these instead of macros over call lists.
+template <bool V> using bool_c = std::integral_constant<bool, V>;
+template <class Fn> int with_bool(bool v, Fn&& fn) { return v ? fn(bool_c<true>{}) : fn(bool_c<false>{}); }
+template <int... Vs, class Fn> int with_int(int v, Fn&& fn) {
+    int rc = SS_ERR_INVALID;
+    (void)((v == Vs && ((rc = fn(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
 
 // A packed-weight buffer (ss_pack_*): `terms` bytes of split fragments, then -- two-term fp16 forms -- the inverse scales as floats;
 // `total` is the whole buffer, what ss_pack_*_bytes reports.  Each layout's owning .hip file has ONE function that returns this; the

@@ -21,9 +21,9 @@
 // reads the same 16 B per lane per term and step; LDS is left to the activations).
 #include <algorithm>
 #include <stdlib.h>
-#include <type_traits>
 
 #include "common.h"
+#include "conv_plan.h"
 #include "split_f16.h"
 
 // Phase stamps of a workgroup: no-ops here.  tools/conv_timing.hip defines SS_STAMP / SS_STAMP_STEPS_* before including this
@@ -48,9 +48,6 @@ constexpr int KSTEPS = 14;        // ceil(27 taps / 2): the 3-D kernels (BCfg::K
 #endif
 #ifndef SS_A_AHEAD_S2
 #define SS_A_AHEAD_S2 2           // SS_A_AHEAD / SS_ROW_PAIR of the stride-2 form (3, 4 steps ahead / row pairs: all within +-1.5 us of 90)
-#endif
-#ifndef SS_S2_MS_MIN_WGS
-#define SS_S2_MS_MIN_WGS 256      // stride 2: fewest 64-channel workgroups for which the waves split the channels (below: one 32-channel tile per workgroup; 128 on the 128-workgroup layer: 29.5 vs 26.4 us)
 #endif
 #ifndef SS_ROW_PAIR_S2
 #define SS_ROW_PAIR_S2 1
@@ -118,18 +115,10 @@ constexpr int gather_slots(bool gather, int S, int TD, int TH, int KD) {
 // head form (HEAD of the kernel): the 32 -> 1 head's weight fragments, [3 bf16 terms][2 K-steps][64 lanes] 16-byte slots
 constexpr int HEAD_WSLOTS = 3 * 2 * 64;
 constexpr int HEAD_PATCH = 6 * 6 * 34;        // a 4 x 4 x 32 tile's contributions to the head's output: its positions and one ring around them
+// the bits of the kernel's `relu` word (launch_conv packs them from ConvArgs' three booleans)
+constexpr int RELU_BIT = 1, RES_PRE_BIT = 2, OUT_CL_BIT = 4;
 
-// Chunk-blocked accumulation (ACCB of the kernel) is a property of the LAYER, never of the tile a launch happens to get: the
-// tile candidates depend on the batch size, and a pair must get the same bits alone and in a batch
-// (test_hot_segment_batch_invariance_at_the_sharded_batch_sizes).  fp16 form only.  It is on for every stride-2 layer, every
-// 2-D layer, and the stride-1 3-D layers that at batch 1 are too small for the 4-row tile -- the deep, narrow layers with the
-// longest K (conv2 / conv4 of the hourglasses: K = 1728 / 3456): there the second accumulator set fits the registers of the 1- and
-// 2-row tiles they run on at small batch; when a larger batch -- or the fill hint of a pipelined call -- moves them onto the 4-row
-// tile, that variant walks the chunk in two passes of two rows (acc_passes above; one pass with a second set for all four rows
-// spilled 15 - 46 registers).  The big 4-row layers (concat_stem, classif.0, hourglass2.conv2) keep the single chain.
-#ifndef SS_ACC_BLOCKED
-#define SS_ACC_BLOCKED 1                  // 0: single chains everywhere (tools/build_variant.sh, for A/B measurements)
-#endif
+// (ACCB of the kernel, chunk-blocked accumulation, is a property of the LAYER: conv_plan.h decides it)
 
 // GATED: the channelAtt gate is fused into the epilogue (only concat_stem has one, so its launches also carry
 // their own kernel symbol in a profile: conv3d_bf16s<..., true>)
@@ -235,12 +224,12 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
     // relu bit 0: ReLU; bit 1: `residual` is added BEFORE the affine: a partial sum of the same convolution computed
     // elsewhere (stem_left.hip).  It joins the accumulator in the epilogue, fetched together with the gate (as initial
     // accumulators its 64 loads per lane were 14 k cycles of every workgroup's prologue: tools/wg_phases.py).
-    const bool res_pre = (relu & 2) != 0 && residual != nullptr;
+    const bool res_pre = (relu & RES_PRE_BIT) != 0 && residual != nullptr;
     // bit 2: CHANNELS-LAST output [Do][Ho][Wo][Cout] (the hand-off to the 32 -> 1 head of the same classifier, conv3d_head.hip,
     // which wants 8 consecutive channels of a position per lane): a lane's 4 consecutive channels of a fragment register
     // group go out as one 16-byte store instead of four 4-byte ones.  Plain stride-1 form only, Cout % 8 == 0.
     constexpr bool CAN_CL = !GATED && MT == 1 && S == 1 && KD == 3;
-    const bool out_cl = CAN_CL && (relu & 4) != 0;
+    const bool out_cl = CAN_CL && (relu & OUT_CL_BIT) != 0;
     // f16 form: float[Cout] of 2^-(weight scale of the channel), stored behind the packed terms (must agree with conv_packed().terms)
     const float* wunscale = reinterpret_cast<const float*>(
         reinterpret_cast<const char*>(wsplit) + (size_t)((Cin + 7) / 8) * C::KSTEPS * ((NTERMS == F16X3 ? 2 : 3) * 2 * Cout * 16));
@@ -669,7 +658,7 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
         int ow0, oh0, od0;
         tile_origin(tile, ow0, oh0, od0);
         const float hunscale = bexp.acc_unscale();
-        const float hfloor = (relu & 1) ? 0.f : -__builtin_inff();
+        const float hfloor = (relu & RELU_BIT) ? 0.f : -__builtin_inff();
         const bool colok = ow0 + l31 < Wo && od0 + dzw < Do;
         // ---- t[tap row][position] of this wave's rows: the accumulators become the B operand as they are ----
 #ifndef SS_EXP_HEAD_NOT           // (timing experiment, wrong results: the head's contraction skipped)
@@ -771,7 +760,7 @@ __global__ __launch_bounds__(256, (NTERMS == F16X3) ? SS_F16_WGS : 2) void conv3
     const __amdgpu_buffer_rsrc_t gres = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(GATED ? gate + (size_t)b * Cout * out_plane : obase), 0,
         GATED ? (int)min((long long)Cout * (long long)gchan_b, 0x7fffffffLL) : 0, 0x00020000);
-    const float floor_v = (relu & 1) ? 0.f : -__builtin_inff();
+    const float floor_v = (relu & RELU_BIT) ? 0.f : -__builtin_inff();
     // the side inputs (affine, gate, residual) of a group of EG fragment rows are fetched first so that their latencies
     // overlap instead of chaining; every group costs one exposed round trip (load -> store -> the next group's loads)
     // (the next tile's first chunk occupies the prefetch registers during the epilogue: with both a gate and a residual to
@@ -919,142 +908,167 @@ __global__ __launch_bounds__(256) void pack_weights_f16s_fused_kernel(const floa
 
 #endif  // !SS_CONV_GATHER_TU
 
-template <int S, int NT, int TD, int TH, int NTERMS, bool GATED, int MT, int KD = 3, int MS = 1, bool ACCB = false, bool GATHER = false, bool HEAD = false, bool CAT = false>
-int launch_bgm(const float* in, const void* wsplit, const float* scale, const float* shift, const float* residual,
-              const float* gate, float* out, int B, int Cin, int D, int H, int W, int Cout, int relu, hipStream_t st,
-              const float* cand = nullptr, const float* catt = nullptr, const float* in2 = nullptr, int bsplit = 0, int csplit = 0) {
-    using C = BCfg<S, NT, TD, TH, KD, (NTERMS == 6) ? 3 : 2, wlds_form(S, NT, NTERMS, MT, KD, GATHER, ACCB) ? ((KD * 9 + 1) / 2) * 2 * 64 : 0, MS,
-                   gather_slots(GATHER, S, TD, TH, KD) + (HEAD ? HEAD_WSLOTS : 0)>;
-    const int Do = (D + 2 * (KD / 2) - KD) / S + 1, Ho = (H - 1) / S + 1, Wo = (W - 1) / S + 1;
+// ---- host side: a launch's arguments by NAME (the entry points fill them), an instantiation by what it SETS ----
+static_assert(ss::kNtermsF16 == F16X3, "conv_plan.h and split_f16.h name the same engine");
+struct ConvArgs {
+    const float* in = nullptr;                                  // [B,Cin,D,H,W]; gather form: the 2-D right feature map [B,Cin,H,W]; concat-free form: channels [0, csplit)
+    const float* in_second_view = nullptr; int bsplit = 0;      // batch elements >= bsplit come from this tensor instead (ss_conv2d_bf16s_pair_fwd)
+    const void* wsplit = nullptr;                               // ss_pack_conv{3d,2d}_weights_*
+    const float *scale = nullptr, *shift = nullptr;             // the folded BatchNorm (null: 1 / 0)
+    const float* residual = nullptr;                            // added after the affine, or (residual_is_partial_sum) before it
+    const float* gate = nullptr;                                // channelAtt gate [B,Cout,H,W]
+    float* out = nullptr;                                       // head form: the patch buffer
+    const float *candidates = nullptr, *attention = nullptr;    // gather form: [B,D,H,W] each
+    const void* head_weights = nullptr;                         // head form: ss_pack_classifier_head_weights
+    const float *rem = nullptr, *rem_second_view = nullptr; int csplit = 0;      // concat-free form: channels [csplit, Cin)
+    int B = 0, Cin = 0, D = 1, H = 0, W = 0, Cout = 0;          // the INPUT's extents (gather form: D = the number of candidates)
+    hipStream_t stream = nullptr;  bool relu = false, residual_is_partial_sum = false, channels_last = false;
+};
+
+// One instantiation of conv3d_bf16s, named by what it sets: ConvForm<S, NT, TD, TH, NTERMS> is the plain form of a tile and each member
+// returns the form with one thing changed -- ConvForm<1, 4, 4, 4, F16X3>{}.head().  Nobody else spells the thirteen positions.  The kernel's
+// and BCfg's static_asserts are reached through launch_conv; the assert here holds the launchers' own rules.
+template <int S_, int NT_, int TD_, int TH_, int NTERMS_, bool GATED_, int MT_, int KD_, int MS_, bool ACCB_, bool GATHER_, bool HEAD_, bool CAT_>
+struct ConvFormT {
+    static constexpr int S = S_, NT = NT_, TD = TD_, TH = TH_, NTERMS = NTERMS_, MT = MT_, KD = KD_, MS = MS_;
+    static constexpr bool GATED = GATED_, ACCB = ACCB_, GATHER = GATHER_, HEAD = HEAD_, CAT = CAT_;
+    static_assert((MT == 1 || S == 2) && (MS == 1 || (S == 2 && !GATED)), "two channel tiles per wave, split channels: stride 2 only; no gated split form (it would spill)");
+    template <bool V = true> constexpr auto gated(ss::bool_c<V> = {}) const { return ConvFormT<S, NT, TD, TH, NTERMS, V, MT, KD, MS, ACCB, GATHER, HEAD, CAT>{}; }
+    template <bool V = true> constexpr auto accb(ss::bool_c<V> = {}) const { return ConvFormT<S, NT, TD, TH, NTERMS, GATED, MT, KD, MS, V, GATHER, HEAD, CAT>{}; }
+    template <bool V = true> constexpr auto cat(ss::bool_c<V> = {}) const { return ConvFormT<S, NT, TD, TH, NTERMS, GATED, MT, KD, MS, ACCB, GATHER, HEAD, V>{}; }
+    constexpr auto gather() const { return ConvFormT<S, NT, TD, TH, NTERMS, GATED, MT, KD, MS, ACCB, true, HEAD, CAT>{}; }
+    constexpr auto head() const { return ConvFormT<S, NT, TD, TH, NTERMS, GATED, MT, KD, MS, ACCB, GATHER, true, CAT>{}; }
+    constexpr auto conv2d() const { return ConvFormT<S, NT, TD, TH, NTERMS, GATED, MT, 1, MS, ACCB, GATHER, HEAD, CAT>{}; }          // 3x3 over depth-1 volumes
+    constexpr auto two_channel_tiles() const { return ConvFormT<S, NT, TD, TH, NTERMS, GATED, 2, KD, MS, ACCB, GATHER, HEAD, CAT>{}; }   // per wave (MT)
+    // the waves split the workgroup's 64 channels (MS = 2): a wave is (row pair, 32 channels) and owns twice the rows
+    constexpr auto split_channels() const { return ConvFormT<S, 2 * NT, TD, TH, NTERMS, GATED, MT, KD, 2, ACCB, GATHER, HEAD, CAT>{}; }
+};
+template <int S, int NT, int TD, int TH, int NTERMS>
+using ConvForm = ConvFormT<S, NT, TD, TH, NTERMS, false, 1, 3, 1, false, false, false, false>;
+
+// The ONE function that knows how the kernel's trailing parameters alias: `cand` carries the candidates (gather form), the packed
+// head weights (head form) or rem (concat-free form), `catt` the attention weights or rem_second_view, `relu` the three booleans.
+template <class F>
+int launch_conv(F, const ConvArgs& a) {
+    constexpr int S = F::S, TD = F::TD, TH = F::TH, KD = F::KD, MT = F::MT, MS = F::MS;
+    // (fields the form cannot use stay null; channels-last output: the plain stride-1 3-D forms)
+    SS_REQUIRE(F::GATED == (a.gate != nullptr) && (F::GATHER || (!a.candidates && !a.attention)) && (F::HEAD || !a.head_weights));
+    SS_REQUIRE((F::CAT || (!a.rem && !a.rem_second_view && a.csplit == 0)) && (!F::HEAD || !a.residual));
+    SS_REQUIRE(!a.channels_last || (!F::GATED && !F::HEAD && MT == 1 && S == 1 && KD == 3));
+    const float* cand = F::GATHER ? a.candidates : (F::HEAD ? reinterpret_cast<const float*>(a.head_weights) : a.rem);
+    const float* catt = F::GATHER ? a.attention : a.rem_second_view;
+    const int relu = (a.relu ? RELU_BIT : 0) | (a.residual_is_partial_sum ? RES_PRE_BIT : 0) | (a.channels_last ? OUT_CL_BIT : 0);
+    using C = BCfg<S, F::NT, TD, TH, KD, (F::NTERMS == 6) ? 3 : 2, wlds_form(S, F::NT, F::NTERMS, MT, KD, F::GATHER, F::ACCB) ? ((KD * 9 + 1) / 2) * 2 * 64 : 0, MS,
+                   gather_slots(F::GATHER, S, TD, TH, KD) + (F::HEAD ? HEAD_WSLOTS : 0)>;
+    const int Do = (a.D + 2 * (KD / 2) - KD) / S + 1, Ho = (a.H - 1) / S + 1, Wo = (a.W - 1) / S + 1;
     const int tiles_w = ss::ceil_div(Wo, 32), tiles_h = ss::ceil_div(Ho, TH), tiles_d = ss::ceil_div(Do, TD);
     const long long nt = (long long)tiles_w * tiles_h * tiles_d;
-    if (nt > 0x7fffffffLL || B > 65535) return SS_ERR_UNSUPPORTED;
-    auto kern = conv3d_bf16s<S, NT, TD, TH, NTERMS, GATED, MT, KD, MS, ACCB, GATHER, HEAD, CAT>;
+    if (nt > 0x7fffffffLL || a.B > 65535) return SS_ERR_UNSUPPORTED;
+    auto kern = conv3d_bf16s<S, F::NT, TD, TH, F::NTERMS, F::GATED, MT, KD, MS, F::ACCB, F::GATHER, F::HEAD, F::CAT>;
     if (C::LDS_BYTES > 64 * 1024) {
         if (ss::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)C::LDS_BYTES) != SS_OK) return SS_ERR_LAUNCH;
     }
     // persistent workgroups: as many as the chip holds at once (2 - 4 per CU depending on the tile), each walking an equal
     // share of the tiles
-    const int groups = ss::ceil_div(Cout, 32 * MT * MS) * B;
+    const int groups = ss::ceil_div(a.Cout, 32 * MT * MS) * a.B;
     const long long cap = std::max<long long>(1, ss::resident_workgroups(reinterpret_cast<const void*>(kern), 256, (int)C::LDS_BYTES) / groups);
     const long long rounds = ss::ceil_div_ll(nt, cap);
     const long long gx = ss::ceil_div_ll(nt, rounds);
-    dim3 grid((unsigned)gx, ss::ceil_div(Cout, 32 * MT * MS), B);
+    dim3 grid((unsigned)gx, ss::ceil_div(a.Cout, 32 * MT * MS), a.B);
     // (Workgroups of equal duration that all start together stay in lock-step -- every CU stages, multiplies and stores at
     // the same time.  Starting the first round's workgroups spread over 0.5-1.5 estimated lifetimes, in 2-16 groups, was
     // measured: no gain, -0 .. -8 %.)
-    hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS_BYTES, st, in, reinterpret_cast<const uint4*>(wsplit), scale, shift,
-                       residual, gate, out, Cin, D, H, W, Cout, Do, Ho, Wo, tiles_w, tiles_h, (int)nt, relu, cand, catt, in2, bsplit, csplit);
+    hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS_BYTES, a.stream, a.in, reinterpret_cast<const uint4*>(a.wsplit), a.scale, a.shift,
+                       a.residual, a.gate, a.out, a.Cin, a.D, a.H, a.W, a.Cout, Do, Ho, Wo, tiles_w, tiles_h, (int)nt, relu, cand, catt,
+                       a.in_second_view, a.bsplit, a.csplit);
     return ss::check_launch();
 }
 
-#ifndef SS_CONV_GATHER_TU
-template <int S, int NT, int TD, int TH, int NTERMS, bool GATED, bool ACCB>
-int launch_bg(const float* in, const void* wsplit, const float* scale, const float* shift, const float* residual,
-              const float* gate, float* out, int B, int Cin, int D, int H, int W, int Cout, int relu, hipStream_t st) {
-    // stride 2: two output tiles per wave (the activation staging is then shared: 154 vs 191 us on the largest layer)
-    // unless that leaves fewer workgroups than CUs (57 vs 41 us on the smallest)
-    const int Do = (D - 1) / S + 1, Ho = (H - 1) / S + 1, Wo = (W - 1) / S + 1;
-    // (ss::fill_hint(): pairs in flight on the chip beside this launch's own -- the fill thresholds below count their workgroups too)
-    const long long wg2 = (long long)ss::ceil_div(Wo, 32) * ss::ceil_div(Ho, TH) * ss::ceil_div(Do, TD) * ss::ceil_div(Cout, 64) * B * ss::fill_hint();
-    // ... and, since r03, the 64 channels split over the waves (MS = 2: wave = (row pair, 32 channels)) instead of two channel
-    // tiles per wave: the same MFMAs and staging with half the weight-fragment fetches (SS_CONV_S2_MT1=0: the r02 form)
-    if constexpr (S == 2 && NT == 1 && TD * TH == 4 && !GATED) {      // (no layer gates a stride-2 conv; its MS form would spill)
-        if (Cout > 32 && wg2 >= SS_S2_MS_MIN_WGS && ss::tuning().conv_s2_mt1 < 0)
-            return launch_bgm<S, 2, TD, TH, NTERMS, GATED, 1, 3, 2, ACCB>(in, wsplit, scale, shift, residual, gate, out, B, Cin, D, H, W, Cout, relu, st);
+// ---- runtime -> compile time (ss::with_bool / ss::with_int): exactly the instantiations that are built -- chunk-blocked accumulation
+// in the fp16 form only, two channel tiles per wave at stride 2 only, no gated split-channel form ----
+// the stride-1 tile candidates of ss::plan_conv3d as forms (a new candidate: one row there, one arm here)
+template <int NTERMS, class Fn>
+int with_stride1_tile(ss::Tile3 tile, Fn&& fn) {
+    switch (tile) {
+        case ss::Tile3::t4x4x32: return fn(ConvForm<1, 4, 4, 4, NTERMS>{});
+        case ss::Tile3::t2x8x32: return fn(ConvForm<1, 4, 2, 8, NTERMS>{});
+        case ss::Tile3::t1x8x32: return fn(ConvForm<1, 2, 1, 8, NTERMS>{});
+        default: return fn(ConvForm<1, 1, 1, 4, NTERMS>{});
     }
-    if (S == 2 && Cout > 32 && wg2 >= 256 && ss::tuning().conv_s2_mt1 <= 0)
-        return launch_bgm<S, NT, TD, TH, NTERMS, GATED, (S == 2) ? 2 : 1, 3, 1, ACCB>(in, wsplit, scale, shift, residual, gate, out, B, Cin, D, H, W,
-                                                                                      Cout, relu, st);
-    return launch_bgm<S, NT, TD, TH, NTERMS, GATED, 1, 3, 1, ACCB>(in, wsplit, scale, shift, residual, gate, out, B, Cin, D, H, W, Cout, relu, st);
 }
-
-template <int S, int NT, int TD, int TH, int NTERMS>
-int launch_b(const float* in, const void* wsplit, const float* scale, const float* shift, const float* residual,
-             const float* gate, float* out, int B, int Cin, int D, int H, int W, int Cout, int relu, bool accb, hipStream_t st) {
-    if constexpr (NTERMS == F16X3) {
-        if (accb) {
-            if (gate != nullptr)
-                return launch_bg<S, NT, TD, TH, NTERMS, true, true>(in, wsplit, scale, shift, residual, gate, out, B, Cin, D, H, W, Cout, relu, st);
-            return launch_bg<S, NT, TD, TH, NTERMS, false, true>(in, wsplit, scale, shift, residual, gate, out, B, Cin, D, H, W, Cout, relu, st);
-        }
-    }
-    if (gate != nullptr)
-        return launch_bg<S, NT, TD, TH, NTERMS, true, false>(in, wsplit, scale, shift, residual, gate, out, B, Cin, D, H, W, Cout, relu, st);
-    return launch_bg<S, NT, TD, TH, NTERMS, false, false>(in, wsplit, scale, shift, residual, gate, out, B, Cin, D, H, W, Cout, relu, st);
+// a 3-D tile with the layer's gate and accumulation
+template <class Tile, class Fn>
+int with_gate_and_accb(Tile tile, bool gated, bool accb, Fn&& fn) {
+    return ss::with_bool(gated, [&](auto g) {
+        if constexpr (Tile::NTERMS != F16X3) return fn(tile.gated(g));
+        else return ss::with_bool(accb, [&](auto b) { return fn(tile.gated(g).accb(b)); });
+    });
 }
-
-#endif  // !SS_CONV_GATHER_TU
 
 }  // namespace
 
 #ifndef SS_CONV_GATHER_TU
-static int conv3d_bf16s_impl(const float* in, const void* wsplit, const float* scale, const float* shift,
-                             const float* residual, const float* gate, float* out, int B, int Cin, int D, int H,
-                             int W, int Cout, int stride, int relu, int nterms, ss_stream_t stream);
+static int check_conv_args(const ConvArgs& a, int nterms) {      // (2-D: D = 1)
+    SS_REQUIRE(a.in && a.wsplit && a.out && a.B > 0 && a.Cin > 0 && a.D > 0 && a.H > 0 && a.W > 0 && a.Cout > 0);
+    SS_REQUIRE((nterms == 3 || nterms == 6 || nterms == F16X3) && (reinterpret_cast<uintptr_t>(a.wsplit) & 15) == 0);
+    // operands are addressed through 32-bit buffer offsets: one batch element's input must stay below 2 GiB
+    return (long long)a.Cin * a.D * a.H * a.W * 4 >= 0x7fffffffLL ? SS_ERR_UNSUPPORTED : SS_OK;
+}
+
+static int conv3d_bf16s_impl(const ConvArgs& a, int stride, int nterms) {
+    SS_REQUIRE(stride == 1 || stride == 2);
+    if (const int rc = check_conv_args(a, nterms); rc != SS_OK) return rc;
+    const int Do = (a.D - 1) / stride + 1, Ho = (a.H - 1) / stride + 1, Wo = (a.W - 1) / stride + 1;
+    if ((long long)a.Cout * Do * Ho * Wo * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;      // ... and so must its output
+    const ss::ConvPlan plan = ss::plan_conv3d(Do, Ho, Wo, a.Cout, a.B, stride, nterms, a.gate != nullptr, ss::fill_hint(),
+                                              ss::tuning().conv_tile, ss::tuning().conv_s2_mt1);
+    return ss::with_int<3, 6, F16X3>(nterms, [&](auto nt) {
+        auto launch = [&](auto tile) {
+            return with_gate_and_accb(tile, a.gate != nullptr, plan.accb, [&](auto form) {
+                using F = decltype(form);
+                if constexpr (F::S == 2 && !F::GATED) {
+                    if (plan.s2 == ss::S2Form::split_channels) return launch_conv(form.split_channels(), a);
+                }
+                if constexpr (F::S == 2) {
+                    if (plan.s2 == ss::S2Form::two_channel_tiles) return launch_conv(form.two_channel_tiles(), a);
+                }
+                return launch_conv(form, a);
+            });
+        };
+        // stride 2 needs a 65-column halo tile per row.  A 1 x 4 output tile is 84 KB of split operands: one workgroup per
+        // CU, slower than the exact-fp32 kernel (283 vs 229 us on the largest layer).  A 2 x 2 tile is 78 KB (5 x 5 x 65 halo positions): two
+        // workgroups per CU, faster on every stride-2 layer of the model (190 / 95 / 68 / 41 us vs 229 / 122 / 81 / 62).
+        if (stride == 2) return launch(ConvForm<2, 1, 2, 2, decltype(nt)::value>{});
+        return with_stride1_tile<decltype(nt)::value>(plan.tile, launch);
+    });
+}
 
 extern "C" int ss_conv3d_bf16s_fwd(const float* in, const void* wsplit, const float* scale, const float* shift,
                                    const float* residual, const float* gate, float* out, int B, int Cin, int D, int H,
                                    int W, int Cout, int stride, int relu, int nterms, ss_stream_t stream) {
-    return conv3d_bf16s_impl(in, wsplit, scale, shift, residual, gate, out, B, Cin, D, H, W, Cout, stride, relu ? 1 : 0, nterms,
-                             stream);
+    ConvArgs a;
+    a.in = in; a.wsplit = wsplit; a.scale = scale; a.shift = shift; a.residual = residual; a.gate = gate; a.out = out;
+    a.B = B; a.Cin = Cin; a.D = D; a.H = H; a.W = W; a.Cout = Cout; a.relu = relu != 0; a.stream = ss::as_stream(stream);
+    return conv3d_bf16s_impl(a, stride, nterms);
 }
 
 extern "C" int ss_conv3d_bf16s_partial_fwd(const float* in, const void* wsplit, const float* partial, const float* scale,
                                            const float* shift, const float* gate, float* out, int B, int Cin, int D,
                                            int H, int W, int Cout, int relu, int nterms, ss_stream_t stream) {
     SS_REQUIRE(partial != nullptr);
-    return conv3d_bf16s_impl(in, wsplit, scale, shift, partial, gate, out, B, Cin, D, H, W, Cout, 1, (relu ? 1 : 0) | 2, nterms,
-                             stream);
+    ConvArgs a;
+    a.in = in; a.wsplit = wsplit; a.scale = scale; a.shift = shift; a.residual = partial; a.residual_is_partial_sum = true; a.gate = gate; a.out = out;
+    a.B = B; a.Cin = Cin; a.D = D; a.H = H; a.W = W; a.Cout = Cout; a.relu = relu != 0; a.stream = ss::as_stream(stream);
+    return conv3d_bf16s_impl(a, 1, nterms);
 }
 
 extern "C" int ss_conv3d_bf16s_cl_fwd(const float* in, const void* wsplit, const float* scale, const float* shift, float* out,
                                       int B, int Cin, int D, int H, int W, int Cout, int relu, int nterms, ss_stream_t stream) {
     SS_REQUIRE(Cout > 0 && Cout % 8 == 0);
-    return conv3d_bf16s_impl(in, wsplit, scale, shift, nullptr, nullptr, out, B, Cin, D, H, W, Cout, 1, (relu ? 1 : 0) | 4, nterms,
-                             stream);
-}
-
-static int conv3d_bf16s_impl(const float* in, const void* wsplit, const float* scale, const float* shift,
-                                   const float* residual, const float* gate, float* out, int B, int Cin, int D, int H,
-                                   int W, int Cout, int stride, int relu, int nterms, ss_stream_t stream) {
-    SS_REQUIRE(in && wsplit && out);
-    SS_REQUIRE(B > 0 && Cin > 0 && D > 0 && H > 0 && W > 0 && Cout > 0);
-    SS_REQUIRE((stride == 1 || stride == 2) && (nterms == 3 || nterms == 6 || nterms == F16X3));
-    SS_REQUIRE((reinterpret_cast<uintptr_t>(wsplit) & 15) == 0);
-    // operands are addressed through 32-bit buffer offsets: one batch element's input must stay below 2 GiB
-    if ((long long)Cin * D * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
-    hipStream_t st = ss::as_stream(stream);
-    const int Do = (D - 1) / stride + 1, Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    if ((long long)Cout * Do * Ho * Wo * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;      // ... and so must its output
-    auto blocks = [&](int td, int th) {
-        return (long long)ss::ceil_div(Wo, 32) * ss::ceil_div(Ho, th) * ss::ceil_div(Do, td) * ss::ceil_div(Cout, 32) * B;
-    };
-    const int forced = ss::tuning().conv_tile;
-    // The tile is chosen for FILL: the largest whose workgroups still cover the chip.  A launch that shares the chip with other pairs'
-    // launches (PairPipeline's lanes) is not alone in filling it: ss::fill_hint() scales the count by the pairs in flight.  Every tile
-    // gives the same bits (the summation order is the layer's, see ACCB), so the hint -- and a race on it -- changes speed only.
-    const long long hint = ss::fill_hint();
-    int tile = (blocks(2, 8) * hint >= 512) ? 0 : ((blocks(1, 8) * hint >= 512) ? 1 : 2);
-    if (forced >= 0 && forced <= 2) tile = forced;
-    // chunk-blocked accumulation: decided by the LAYER (what ONE pair of it offers the chip), not by this launch's batch or tile
-    const bool small_layer = blocks(2, 8) / B < 512;
-    const bool accb = SS_ACC_BLOCKED && nterms == F16X3 && (stride == 2 || small_layer);
-#define SS_B(S, NT, TD, TH)                                                                                              \
-    return (nterms == 6) ? launch_b<S, NT, TD, TH, 6>(in, wsplit, scale, shift, residual, gate, out, B, Cin, D, H, W, Cout, relu, accb, st) \
-         : (nterms == 3) ? launch_b<S, NT, TD, TH, 3>(in, wsplit, scale, shift, residual, gate, out, B, Cin, D, H, W, Cout, relu, accb, st) \
-                         : launch_b<S, NT, TD, TH, F16X3>(in, wsplit, scale, shift, residual, gate, out, B, Cin, D, H, W, Cout, relu, accb, st)
-    // stride 2 needs a 65-column halo tile per row.  A 1 x 4 output tile is 84 KB of split operands: one workgroup per
-    // CU, slower than the exact-fp32 kernel (283 vs 229 us on the largest layer).  A 2 x 2 tile is 78 KB: two
-    // workgroups per CU, faster on every stride-2 layer of the model (190 / 95 / 68 / 41 us vs 229 / 122 / 81 / 62).
-    if (stride == 2) { SS_B(2, 1, 2, 2); }     // 5 x 5 x 65 halo positions: 78 KB of split operands, two workgroups per CU
-    // 4 planes x 4 rows: the most compact halo (6 x 6 x 34 = 1224 positions against 1360 for 2 x 8: -3 % time, 8 fewer
-    // prefetch registers); 2 x 8 when the depth is not a multiple of 4
-    if (tile == 0 && Do % 4 == 0) { SS_B(1, 4, 4, 4); }
-    if (tile == 0) { SS_B(1, 4, 2, 8); }
-    if (tile == 1) { SS_B(1, 2, 1, 8); }
-    SS_B(1, 1, 1, 4);
-#undef SS_B
+    ConvArgs a;
+    a.in = in; a.wsplit = wsplit; a.scale = scale; a.shift = shift; a.out = out; a.channels_last = true;
+    a.B = B; a.Cin = Cin; a.D = D; a.H = H; a.W = W; a.Cout = Cout; a.relu = relu != 0; a.stream = ss::as_stream(stream);
+    return conv3d_bf16s_impl(a, 1, nterms);
 }
 
 // The packed weights of the 3x3x3 (ktaps 27) and 3x3 (ktaps 9) convs, the one statement of their size:
@@ -1106,44 +1120,39 @@ extern "C" int ss_pack_conv2d_weights_f16s(const float* w, void* wsplit, int Cou
 }
 extern "C" int ss_pack_conv2d_weights_f16s_bytes(int Cout, int Cin, long long* bytes) { return conv_packed_bytes(Cout, Cin, 9, true, bytes); }
 
-static int conv2d_bf16s_impl(const float* in, const float* in2, int bsplit, const void* wsplit, const float* scale, const float* shift,
-                            const float* residual, float* out, int B, int Cin, int H, int W, int Cout, int relu,
-                            int nterms, ss_stream_t stream);
-static int conv2d_bf16s_cat_impl(const float* x_a, const float* x_b, const float* rem_a, const float* rem_b, int bsplit, int csplit,
-                                const void* wsplit, const float* scale, const float* shift, float* out, int B, int Cin, int H, int W,
-                                int Cout, int relu, int nterms, ss_stream_t stream);
+// (the plain and the concat-free form -- a.rem set -- get the same tile for the same launch: the two are bit-identical)
+static int conv2d_bf16s_impl(const ConvArgs& a, int nterms) {
+    if (const int rc = check_conv_args(a, nterms); rc != SS_OK) return rc;
+    const int rows = ss::plan_conv2d_rows(a.H, a.W, a.Cout, a.B);
+    return ss::with_int<3, 6, F16X3>(nterms, [&](auto nt) {
+        constexpr int NTERMS = decltype(nt)::value;
+        auto launch = [&](auto tile) {
+            const auto form = tile.conv2d().accb(ss::bool_c<NTERMS == F16X3 && ss::kConv2dAccb>{});
+            return ss::with_bool(a.rem != nullptr, [&](auto cat) { return launch_conv(form.cat(cat), a); });
+        };
+        if (rows == 16) return launch(ConvForm<1, 4, 1, 16, NTERMS>{});
+        if (rows == 8) return launch(ConvForm<1, 2, 1, 8, NTERMS>{});
+        return launch(ConvForm<1, 1, 1, 4, NTERMS>{});
+    });
+}
 
 extern "C" int ss_conv2d_bf16s_fwd(const float* in, const void* wsplit, const float* scale, const float* shift,
                                    const float* residual, float* out, int B, int Cin, int H, int W, int Cout, int relu,
                                    int nterms, ss_stream_t stream) {
-    return conv2d_bf16s_impl(in, nullptr, 0, wsplit, scale, shift, residual, out, B, Cin, H, W, Cout, relu, nterms, stream);
+    ConvArgs a;
+    a.in = in; a.wsplit = wsplit; a.scale = scale; a.shift = shift; a.residual = residual; a.out = out;
+    a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.relu = relu != 0; a.stream = ss::as_stream(stream);
+    return conv2d_bf16s_impl(a, nterms);
 }
 
 extern "C" int ss_conv2d_bf16s_pair_fwd(const float* in_a, const float* in_b, const void* wsplit, const float* scale,
                                         const float* shift, float* out, int B, int Cin, int H, int W, int Cout, int relu,
                                         int nterms, ss_stream_t stream) {
     SS_REQUIRE(in_a && in_b);
-    return conv2d_bf16s_impl(in_a, in_b, B, wsplit, scale, shift, nullptr, out, 2 * B, Cin, H, W, Cout, relu, nterms, stream);
-}
-
-static int conv2d_bf16s_impl(const float* in, const float* in2, int bsplit, const void* wsplit, const float* scale, const float* shift,
-                            const float* residual, float* out, int B, int Cin, int H, int W, int Cout, int relu,
-                            int nterms, ss_stream_t stream) {
-    SS_REQUIRE(in && wsplit && out);
-    SS_REQUIRE(B > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0 && (nterms == 3 || nterms == 6 || nterms == F16X3));
-    SS_REQUIRE((reinterpret_cast<uintptr_t>(wsplit) & 15) == 0);
-    if ((long long)Cin * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
-    hipStream_t st = ss::as_stream(stream);
-    auto blocks = [&](int th) { return (long long)ss::ceil_div(W, 32) * ss::ceil_div(H, th) * ss::ceil_div(Cout, 32) * B; };
-    const int r = relu ? 1 : 0;
-#define SS_B2(NT, TH)                                                                                                      \
-    return (nterms == 6) ? launch_bgm<1, NT, 1, TH, 6, false, 1, 1>(in, wsplit, scale, shift, residual, nullptr, out, B, Cin, 1, H, W, Cout, r, st, nullptr, nullptr, in2, bsplit) \
-         : (nterms == 3) ? launch_bgm<1, NT, 1, TH, 3, false, 1, 1>(in, wsplit, scale, shift, residual, nullptr, out, B, Cin, 1, H, W, Cout, r, st, nullptr, nullptr, in2, bsplit) \
-                         : launch_bgm<1, NT, 1, TH, F16X3, false, 1, 1, 1, SS_ACC_BLOCKED != 0>(in, wsplit, scale, shift, residual, nullptr, out, B, Cin, 1, H, W, Cout, r, st, nullptr, nullptr, in2, bsplit)
-    if (blocks(16) >= 512) { SS_B2(4, 16); }
-    if (blocks(8) >= 512) { SS_B2(2, 8); }
-    SS_B2(1, 4);
-#undef SS_B2
+    ConvArgs a;
+    a.in = in_a; a.in_second_view = in_b; a.bsplit = B; a.wsplit = wsplit; a.scale = scale; a.shift = shift; a.out = out;
+    a.B = 2 * B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.relu = relu != 0; a.stream = ss::as_stream(stream);
+    return conv2d_bf16s_impl(a, nterms);
 }
 
 // The concat-free form (CAT of the kernel): channels [0, Csplit) of the convolution's input from x_a, [Csplit, Cin) from rem_a; with
@@ -1155,28 +1164,10 @@ extern "C" int ss_conv2d_bf16s_cat_fwd(const float* x_a, const float* rem_a, con
     SS_REQUIRE(B > 0 && Csplit > 0 && Csplit < Cin);
     if (Csplit % 8 != 0) return SS_ERR_UNSUPPORTED;            // a staged 8-channel chunk would straddle the two tensors
     const bool pair = x_b != nullptr;
-    return conv2d_bf16s_cat_impl(x_a, x_b, rem_a, rem_b, pair ? B : 0, Csplit, wsplit, scale, shift, out, pair ? 2 * B : B, Cin, H, W, Cout,
-                                 relu, nterms, stream);
-}
-
-static int conv2d_bf16s_cat_impl(const float* x_a, const float* x_b, const float* rem_a, const float* rem_b, int bsplit, int csplit,
-                                const void* wsplit, const float* scale, const float* shift, float* out, int B, int Cin, int H, int W,
-                                int Cout, int relu, int nterms, ss_stream_t stream) {
-    SS_REQUIRE(wsplit && out);
-    SS_REQUIRE(Cin > 0 && H > 0 && W > 0 && Cout > 0 && (nterms == 3 || nterms == 6 || nterms == F16X3));
-    SS_REQUIRE((reinterpret_cast<uintptr_t>(wsplit) & 15) == 0);
-    if ((long long)Cin * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
-    hipStream_t st = ss::as_stream(stream);
-    // (the same tile choice as conv2d_bf16s_impl for the same launch: the two forms are bit-identical)
-    auto blocks = [&](int th) { return (long long)ss::ceil_div(W, 32) * ss::ceil_div(H, th) * ss::ceil_div(Cout, 32) * B; };
-    const int r = relu ? 1 : 0;
-#define SS_B2C(NT, TH)                                                                                                     \
-    return (nterms == 6) ? launch_bgm<1, NT, 1, TH, 6, false, 1, 1, 1, false, false, false, true>(x_a, wsplit, scale, shift, nullptr, nullptr, out, B, Cin, 1, H, W, Cout, r, st, rem_a, rem_b, x_b, bsplit, csplit) \
-         : (nterms == 3) ? launch_bgm<1, NT, 1, TH, 3, false, 1, 1, 1, false, false, false, true>(x_a, wsplit, scale, shift, nullptr, nullptr, out, B, Cin, 1, H, W, Cout, r, st, rem_a, rem_b, x_b, bsplit, csplit) \
-                         : launch_bgm<1, NT, 1, TH, F16X3, false, 1, 1, 1, SS_ACC_BLOCKED != 0, false, false, true>(x_a, wsplit, scale, shift, nullptr, nullptr, out, B, Cin, 1, H, W, Cout, r, st, rem_a, rem_b, x_b, bsplit, csplit)
-    if (blocks(16) >= 512) { SS_B2C(4, 16); }
-    if (blocks(8) >= 512) { SS_B2C(2, 8); }
-    SS_B2C(1, 4);
-#undef SS_B2C
+    ConvArgs a;
+    a.in = x_a; a.in_second_view = x_b; a.rem = rem_a; a.rem_second_view = rem_b; a.bsplit = pair ? B : 0; a.csplit = Csplit;
+    a.wsplit = wsplit; a.scale = scale; a.shift = shift; a.out = out;
+    a.B = pair ? 2 * B : B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.relu = relu != 0; a.stream = ss::as_stream(stream);
+    return conv2d_bf16s_impl(a, nterms);
 }
 #endif  // !SS_CONV_GATHER_TU

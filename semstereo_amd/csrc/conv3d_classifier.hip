@@ -139,12 +139,13 @@ extern "C" int ss_conv3d_classifier_fused_fwd(const float* in, const void* wspli
     if ((long long)Cin * D * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
     // the form of the LAYER, whatever the batch (a pair gets the same bits alone and in a batch): layers too small for the
     // 4-row tile at batch 1 keep the two-launch form
-    const long long per_pair = (long long)ss::ceil_div(W, 32) * ss::ceil_div(H, 8) * ss::ceil_div(D, 2);
-    if (per_pair < 512) return SS_ERR_UNSUPPORTED;
+    if (ss::small_layer(D, H, W, 32)) return SS_ERR_UNSUPPORTED;
     if (H > 65535 || (long long)B * D > 65535) return SS_ERR_UNSUPPORTED;     // (the patch sum's grid)
     hipStream_t st = ss::as_stream(stream);
-    const int rc = launch_bgm<1, 4, 4, 4, F16X3, false, 1, 3, 1, false, false, true>(
-        in, wsplit, scale, shift, nullptr, nullptr, patches, B, Cin, D, H, W, 32, 1, st, reinterpret_cast<const float*>(head_w));
+    ConvArgs a;
+    a.in = in; a.wsplit = wsplit; a.scale = scale; a.shift = shift; a.head_weights = head_w; a.out = patches;
+    a.B = B; a.Cin = Cin; a.D = D; a.H = H; a.W = W; a.Cout = 32; a.relu = true; a.stream = st;
+    const int rc = launch_conv(ConvForm<1, 4, 4, 4, F16X3>{}.head(), a);
     if (rc != SS_OK || out == nullptr) return rc;
     const int tiles_w = ss::ceil_div(W, 32), tiles_h = ss::ceil_div(H, 4), tiles_d = D / 4;
     hipLaunchKernelGGL(classifier_patch_sum_kernel, dim3(ss::ceil_div(W, 256), H, B * D), dim3(256), 0, st, patches, out, D, H, W, tiles_w,

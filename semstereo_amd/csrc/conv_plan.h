@@ -1,0 +1,67 @@
+// The ONE statement of the conv launchers' tile and accumulation rule (conv3d_bf16s.hip, conv3d_gather.hip, conv3d_classifier.hip):
+// pure functions of integers, host-only, nothing from HIP.  Callers pass ss::fill_hint() and ss::tuning() in.
+#pragma once
+#ifndef SS_S2_MS_MIN_WGS
+#define SS_S2_MS_MIN_WGS 256      // stride 2: fewest 64-channel workgroups for which the waves split the channels (below: one 32-channel tile per workgroup; 128 on the 128-workgroup layer: 29.5 vs 26.4 us)
+#endif
+// Chunk-blocked accumulation (ACCB of the kernel) is a property of the LAYER, never of the tile a launch happens to get: the
+// tile candidates depend on the batch size, and a pair must get the same bits alone and in a batch
+// (test_hot_segment_batch_invariance_at_the_sharded_batch_sizes).  fp16 form only.  It is on for every stride-2 layer, every
+// 2-D layer, and the stride-1 3-D layers that at batch 1 are too small for the 4-row tile -- the deep, narrow layers with the
+// longest K (conv2 / conv4 of the hourglasses: K = 1728 / 3456): there the second accumulator set fits the registers of the 1- and
+// 2-row tiles they run on at small batch; when a larger batch -- or the fill hint of a pipelined call -- moves them onto the 4-row
+// tile, that variant walks the chunk in two passes of two rows (acc_passes of conv3d_bf16s.hip; one pass with a second set for all
+// four rows spilled 15 - 46 registers).  The big 4-row layers (concat_stem, classif.0, hourglass2.conv2) keep the single chain.
+#ifndef SS_ACC_BLOCKED
+#define SS_ACC_BLOCKED 1                  // 0: single chains everywhere (tools/build_variant.sh, for A/B measurements)
+#endif
+
+namespace ss {
+constexpr int kNtermsF16 = 19;            // the ABI's `nterms` code of the two-term fp16 form (F16X3 of split_f16.h)
+constexpr long long kFillWgs = 512;       // workgroups of 32 channels x one tile that fill the chip (two on each of 256 CUs)
+constexpr long long kFillWgsS2 = 256;     // ... of 64 channels x one 2 x 2 x 32 tile (stride 2, two channel tiles per wave)
+
+// the stride-1 3-D tile candidates, planes x rows x columns (4, 4, 2, 1 rows per wave); stride 2 has one tile, 2 x 2 x 32, in three
+// forms: the waves split the workgroup's 64 channels / two 32-channel tiles per wave / one
+enum class Tile3 { t4x4x32, t2x8x32, t1x8x32, t1x4x32 };
+enum class S2Form { split_channels, two_channel_tiles, one_channel_tile };
+struct ConvPlan { Tile3 tile; bool accb; S2Form s2; };      // accb: chunk-blocked accumulation
+
+// workgroups of a launch: td x th x 32 output tiles x tiles of `cpw` channels x batch elements -- what every threshold counts
+constexpr long long blocks(int Do, int Ho, int Wo, int Cout, int B, int td, int th, int cpw = 32) {
+    return (long long)((Wo + 31) / 32) * ((Ho + th - 1) / th) * ((Do + td - 1) / td) * ((Cout + cpw - 1) / cpw) * B;
+}
+// a layer too small for the 4-row tile at batch 1: decided by what ONE pair of it offers the chip, not by a launch's batch or tile
+constexpr bool small_layer(int Do, int Ho, int Wo, int Cout) { return blocks(Do, Ho, Wo, Cout, 1, 2, 8) < kFillWgs; }
+
+// (Do, Ho, Wo): the OUTPUT's extents; hint: pairs in flight on the chip beside this launch's own (ss::fill_hint()) -- the fill
+// thresholds count their workgroups too; forced_tile: ss::tuning().conv_tile; s2_mt1: ss::tuning().conv_s2_mt1
+constexpr ConvPlan plan_conv3d(int Do, int Ho, int Wo, int Cout, int B, int stride, int nterms, bool gated, int hint, int forced_tile, int s2_mt1) {
+    // The tile is chosen for FILL: the largest whose workgroups still cover the chip.  A launch that shares the chip with other pairs'
+    // launches (PairPipeline's lanes) is not alone in filling it: the hint scales the count by the pairs in flight.  Every tile
+    // gives the same bits (the summation order is the layer's, see SS_ACC_BLOCKED), so the hint -- and a race on it -- changes speed only.
+    int tile = (blocks(Do, Ho, Wo, Cout, B, 2, 8) * hint >= kFillWgs) ? 0 : ((blocks(Do, Ho, Wo, Cout, B, 1, 8) * hint >= kFillWgs) ? 1 : 2);
+    if (forced_tile >= 0 && forced_tile <= 2) tile = forced_tile;
+    // 4 planes x 4 rows: the most compact halo (6 x 6 x 34 = 1224 positions against 1360 for 2 x 8: -3 % time, 8 fewer
+    // prefetch registers); 2 x 8 when the depth is not a multiple of 4
+    const Tile3 t = tile == 0 ? (Do % 4 == 0 ? Tile3::t4x4x32 : Tile3::t2x8x32) : (tile == 1 ? Tile3::t1x8x32 : Tile3::t1x4x32);
+    const bool accb = SS_ACC_BLOCKED && nterms == kNtermsF16 && (stride == 2 || small_layer(Do, Ho, Wo, Cout));
+    // stride 2: two output tiles per wave (the activation staging is then shared: 154 vs 191 us on the largest layer)
+    // unless that leaves fewer workgroups than CUs (57 vs 41 us on the smallest)
+    // ... and, since r03, the 64 channels split over the waves (wave = (row pair, 32 channels)) instead of two channel
+    // tiles per wave: the same MFMAs and staging with half the weight-fragment fetches (SS_CONV_S2_MT1=0: the r02 form)
+    // (no layer gates a stride-2 conv; its split form would spill)
+    const long long wg2 = blocks(Do, Ho, Wo, Cout, B, 2, 2, 64) * hint;
+    const S2Form s2 = (Cout > 32 && wg2 >= SS_S2_MS_MIN_WGS && s2_mt1 < 0 && !gated) ? S2Form::split_channels
+                    : (Cout > 32 && wg2 >= kFillWgsS2 && s2_mt1 <= 0)               ? S2Form::two_channel_tiles
+                                                                                    : S2Form::one_channel_tile;
+    return {t, accb, s2};
+}
+
+// the 2-D form (3x3 over [B,C,H,W] maps): rows of the 1 x rows x 32 tile (16, 8 or 4: 4, 2, 1 per wave), the first candidate that
+// fills the chip; chunk-blocked accumulation on every 2-D layer of the fp16 form
+constexpr int plan_conv2d_rows(int H, int W, int Cout, int B) {
+    return blocks(1, H, W, Cout, B, 1, 16) >= kFillWgs ? 16 : (blocks(1, H, W, Cout, B, 1, 8) >= kFillWgs ? 8 : 4);
+}
+constexpr bool kConv2dAccb = SS_ACC_BLOCKED != 0;
+}  // namespace ss

@@ -1,0 +1,170 @@
+"""The conv launchers' tile and accumulation rule (semstereo_amd/csrc/conv_plan.h), checked on the CPU: a probe of a few lines around the
+header is compiled with the system c++ and called through ctypes.
+
+  * chunk-blocked accumulation (what decides the summation order, hence the bits) depends on the LAYER alone: not on the batch, the
+    fill hint or a forced tile;
+  * the Python restatements of the rule in the GPU tests (_rule of tests/test_fill_hint_gpu.py; _s1_form, _s2_form, _stem_form,
+    _conv2d_tile of tests/test_f16_ranges_gpu.py) and engine.classifier_fused_applies give the header's answers;
+  * both sides of every threshold, the forced tile, the depth rule of the 4-row tile, one plan for the plain and the gather entry.
+"""
+import ctypes
+import itertools
+import os
+import subprocess
+
+import pytest
+import torch
+
+import test_f16_ranges_gpu as fr
+import test_fill_hint_gpu as fh
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "semstereo_amd", "csrc")
+PROBE = """
+#include "conv_plan.h"
+extern "C" {
+long long probe_blocks(int Do, int Ho, int Wo, int Cout, int B, int td, int th) { return ss::blocks(Do, Ho, Wo, Cout, B, td, th); }
+void probe_plan3d(int Do, int Ho, int Wo, int Cout, int B, int stride, int nterms, int gated, int hint, int forced, int mt1, int* out) {
+    const ss::ConvPlan p = ss::plan_conv3d(Do, Ho, Wo, Cout, B, stride, nterms, gated != 0, hint, forced, mt1);
+    out[0] = (int)p.tile; out[1] = p.accb; out[2] = (int)p.s2;
+}
+int probe_rows2d(int H, int W, int Cout, int B) { return ss::plan_conv2d_rows(H, W, Cout, B); }
+int probe_small_layer(int D, int H, int W, int Cout) { return ss::small_layer(D, H, W, Cout); }
+int probe_s2_min_wgs() { return SS_S2_MS_MIN_WGS; }
+}
+"""
+TILES = ("4x4x32", "2x8x32", "1x8x32", "1x4x32")          # enum Tile3
+S2FORMS = ("split", "two_tiles", "one_tile")              # enum S2Form, under the names the GPU tests use
+CANDIDATE = {"4x4x32": 0, "2x8x32": 0, "1x8x32": 1, "1x4x32": 2}      # SS_CONV_TILE's number of a tile
+BATCHES, HINTS, FORCED = (1, 2, 4, 8), (1, 3, 6, 64), (-1, 0, 1, 2)
+
+
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    d = tmp_path_factory.mktemp("conv_plan")
+    src, so = d / "probe.cpp", d / "probe.so"
+    src.write_text(PROBE)
+    subprocess.check_call(["c++", "-std=c++17", "-O1", "-Wall", "-Werror", "-shared", "-fPIC", "-I", CSRC, str(src), "-o", str(so)])
+    lib = ctypes.CDLL(str(so))
+    lib.probe_blocks.restype = ctypes.c_longlong
+    return lib
+
+
+def _out(dhw, stride):
+    return tuple((n - 1) // stride + 1 for n in dhw)
+
+
+def plan(lib, out_dhw, cout, B=1, stride=1, nterms=19, gated=False, hint=1, forced=-1, mt1=-1):
+    """-> (tile name, accb, stride-2 form name)"""
+    r = (ctypes.c_int * 3)()
+    lib.probe_plan3d(*out_dhw, cout, B, stride, nterms, int(gated), hint, forced, mt1, r)
+    return TILES[r[0]], bool(r[1]), S2FORMS[r[2]]
+
+
+def _layers():
+    """(Cout, input (D, H, W), stride) of every stride-1 and stride-2 shape the GPU tests of the rule run"""
+    cases = [(c[1], c[2], c[3]) for c in fh.CASES.values()] + [(c[1], c[2], 1) for c in fr.S1_SHAPES.values()]
+    return cases + [(fr.S2_SHAPE[1], fr.S2_SHAPE[2], 2), (fr.LARGE_S1[1], fr.LARGE_S1[2], 1)]
+
+
+def test_accumulation_is_the_layers_not_the_launchs(probe):
+    for cout, dhw, stride in _layers():
+        got = {plan(probe, _out(dhw, stride), cout, B, stride, hint=h, forced=f, mt1=m)[1]
+               for B, h, f, m in itertools.product(BATCHES, HINTS, FORCED, (-1, 0, 1))}
+        want = stride == 2 or fr._s1_form(cout, dhw, 0)[2]
+        assert got == {want}, (cout, dhw, stride, got)
+        for nterms in (3, 6):                   # the bf16 engines have no chunk-blocked form
+            assert not plan(probe, _out(dhw, stride), cout, 1, stride, nterms=nterms)[1]
+
+
+def test_python_restatements_give_the_headers_answers(probe):
+    for case in fh.CASES.values():
+        _cin, cout, dhw, stride = case
+        for hint, B in itertools.product(sorted(set(fh.HINTS + HINTS)), (1, 2)):
+            tile, _accb, s2 = plan(probe, _out(dhw, stride), cout, B, stride, hint=hint)
+            assert fh._rule(case, hint, B) == (CANDIDATE[tile] if stride == 1 else s2), (case, hint, B)
+    for (_cin, cout, dhw), B, forced in itertools.product(list(fr.S1_SHAPES.values()) + [fr.LARGE_S1], (1, 4), (0, 1, 2)):
+        tile, accb, _ = plan(probe, dhw, cout, B, forced=forced)
+        rows, (td, th), want_accb = fr._s1_form(cout, dhw, forced, B)
+        assert (tile, accb) == (f"{td}x{th}x32", want_accb) and rows == {0: 4, 1: 2, 2: 1}[forced]
+    for hint, mt1, B in itertools.product(HINTS, (-1, 0, 1), (1, 2)):
+        _cin, cout, dhw = fr.S2_SHAPE
+        assert plan(probe, _out(dhw, 2), cout, B, 2, hint=hint, mt1=mt1)[2] == fr._s2_form(cout, dhw, hint, mt1, B)
+    for B, C, nd, H, W, forced in fr.STEM:
+        tile, accb, _ = plan(probe, (nd, H, W), C, B, forced=-1 if forced is None else forced)
+        (td, th), want_accb = fr._stem_form(B, C, nd, H, W, forced)
+        assert (tile, accb) == (f"{td}x{th}x32", want_accb)
+    for B, _cs, _cin, cout, H, W in fr.CAT_SHAPES:
+        assert probe.probe_rows2d(H, W, cout, B) == (16, 8, 4)[fr._conv2d_tile(B, cout, H, W)]
+
+
+def test_both_sides_of_every_threshold(probe):
+    # blocks(2, 8) x hint = 511 | 512: 7 x 73 x 1 tiles | 8 x 64 x 1, and 73 tiles x 7 pairs in flight | 64 x 8
+    below, at = (2, 8 * 73, 32 * 7), (2, 8 * 64, 32 * 8)
+    assert probe.probe_blocks(*below, 32, 1, 2, 8) == 511 and probe.probe_blocks(*at, 32, 1, 2, 8) == 512
+    assert plan(probe, below, 32) == ("1x8x32", True, "one_tile") and plan(probe, at, 32)[:2] == ("2x8x32", False)
+    assert plan(probe, (2, 8 * 73, 32), 32, hint=7)[0] == "1x8x32" and plan(probe, (2, 8 * 64, 32), 32, hint=8)[0] == "2x8x32"
+    assert plan(probe, (2, 8 * 73, 32), 32, B=7)[:2] == ("1x8x32", True) and plan(probe, (2, 8 * 64, 32), 32, B=8)[:2] == ("2x8x32", True)
+    assert bool(probe.probe_small_layer(*below, 32)) and not probe.probe_small_layer(*at, 32)
+    # blocks(1, 8) x hint = 511 | 512 with blocks(2, 8) below 512
+    below, at = (1, 8 * 73, 32 * 7), (2, 8 * 32, 32 * 8)
+    assert probe.probe_blocks(*below, 32, 1, 1, 8) == 511 and probe.probe_blocks(*at, 32, 1, 1, 8) == 512
+    assert probe.probe_blocks(*at, 32, 1, 2, 8) == 256
+    assert plan(probe, below, 32)[0] == "1x4x32" and plan(probe, at, 32)[0] == "1x8x32"
+    # stride 2, OUTPUT extents: 17 x 5 x 3 = 255 workgroups of 64 channels | 8 x 8 x 4 = 256
+    assert probe.probe_s2_min_wgs() == 256
+    below, at = (34, 10, 96), (16, 16, 128)
+    for mt1 in (-1, 0, 1):
+        assert plan(probe, below, 64, stride=2, mt1=mt1)[2] == "one_tile"
+    assert [plan(probe, at, 64, stride=2, mt1=m)[2] for m in (-1, 0, 1)] == ["split", "two_tiles", "one_tile"]
+    assert plan(probe, (34, 10, 32), 64, stride=2, hint=3)[2] == "one_tile" and plan(probe, (16, 16, 32), 64, stride=2, hint=4)[2] == "split"
+    assert plan(probe, at, 32, stride=2)[2] == "one_tile"                     # one channel tile: nothing to split or pair
+    assert plan(probe, at, 64, stride=2, gated=True)[2] == "two_tiles"        # no gated split-channel form
+    # the 2-D form: 16, 8 or 4 rows, no hint
+    assert probe.probe_rows2d(16 * 64, 32 * 8, 32, 1) == 16 and probe.probe_rows2d(16 * 73, 32 * 7, 32, 1) == 8
+    assert probe.probe_rows2d(8 * 73, 32 * 7, 32, 1) == 4 and probe.probe_rows2d(8 * 64, 32 * 8, 32, 1) == 8
+
+
+def test_forced_tile_overrides_the_count_and_depth_picks_the_four_row_tile(probe):
+    big, small = (8, 512, 512), (4, 16, 64)
+    assert plan(probe, big, 32)[0] == "4x4x32" and plan(probe, small, 32)[0] == "1x4x32"
+    assert [plan(probe, big, 32, forced=f)[0] for f in (0, 1, 2, 3, -1)] == ["4x4x32", "1x8x32", "1x4x32", "4x4x32", "4x4x32"]
+    assert [plan(probe, small, 32, forced=f)[0] for f in (0, 1, 2, 3)] == ["4x4x32", "1x8x32", "1x4x32", "1x4x32"]
+    for depth, tile in ((4, "4x4x32"), (6, "2x8x32"), (7, "2x8x32"), (24, "4x4x32")):
+        assert plan(probe, (depth, 512, 512), 32)[0] == tile and plan(probe, (depth, 16, 64), 32, forced=0)[0] == tile
+
+
+def test_plain_and_gather_entry_get_one_plan(probe):
+    """ss_conv3d_bf16s_fwd passes the output extents of its stride-1 input, ss_conv3d_gather_fwd (candidates, H, W): the same numbers"""
+    stems = [(B, 32, 24, 256, 256) for B in (1, 4)] + [s[:5] for s in fr.STEM]       # concat_stem at quarter resolution of 1024^2
+    for (B, C, nd, H, W), hint, forced, gated in itertools.product(stems, HINTS, FORCED, (False, True)):
+        assert plan(probe, _out((nd, H, W), 1), C, B, hint=hint, forced=forced, gated=gated) == \
+            plan(probe, (nd, H, W), C, B, hint=hint, forced=forced, gated=gated)
+    for B in (1, 4):
+        assert plan(probe, (24, 256, 256), 32, B)[:2] == ("4x4x32", False)
+
+
+class _Volume:
+    """what engine.classifier_fused_applies reads of a tensor"""
+    is_cuda, dtype = True, torch.float32
+
+    def __init__(self, *shape):
+        self.shape = shape
+
+    def dim(self):
+        return len(self.shape)
+
+
+def test_classifier_rule_is_the_engines_arithmetic(probe):
+    from semstereo_amd import engine
+    # (B, D, H, W) of tests/test_parity_gpu.py and tests/test_f16_ranges_gpu.py, the layer below 512 of the former, 510 | 512 tiles (4 planes: an even count),
+    # and the small maps of the heads' HEAD_SHAPES as 4-, 12- and 24-plane volumes
+    shapes = [(1, 12, 134, 200), (2, 8, 140, 250), (1, 4, 300, 260), (1, 32, 128, 128), (1, 24, 256, 256), (2, 36, 128, 160),
+              (8, 8, 64, 64), (1, 4, 8 * 17, 32 * 15), (1, 4, 8 * 16, 32 * 16), (3, 12, 134, 200)]
+    shapes += [(1, D, H, W) for (_c, H, W), D in itertools.product(fr.HEAD_SHAPES, (4, 12, 24))]
+    served = []
+    for B, D, H, W in shapes:
+        assert D % 4 == 0
+        want = engine.classifier_fused_applies(_Volume(B, 32, D, H, W), 19)
+        assert want == (not probe.probe_small_layer(D, H, W, 32)), (B, D, H, W)
+        served.append(want)
+    assert served[:10] == [True] * 6 + [False, False, True, True] and not any(served[10:])

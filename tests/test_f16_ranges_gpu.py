@@ -431,7 +431,7 @@ S2_SHAPE = (32, 64, (4, 16, 64))
 
 
 def _s2_form(Cout, dhw, hint, mt1, B=1):
-    """launch_bg: the waves split 64 channels (count alone) / two channel tiles per wave (SS_CONV_S2_MT1=0) / one tile per wave"""
+    """ss::plan_conv3d (csrc/conv_plan.h), stride 2: the waves split 64 channels (count alone) / two channel tiles per wave (SS_CONV_S2_MT1=0) / one tile per wave"""
     do, ho, wo = [(n - 1) // 2 + 1 for n in dhw]
     wg2 = _cdiv(wo, 32) * _cdiv(ho, 2) * _cdiv(do, 2) * _cdiv(Cout, 64) * B * hint
     if Cout > 32 and wg2 >= 256 and mt1 < 0:
@@ -484,7 +484,7 @@ def _judged_planes(D, td, slab):
 @pytest.mark.parametrize("order", ["1e+6_then_1e-6", "1e-6_then_1e+6"])
 @pytest.mark.parametrize("tile", [0, 2])
 def test_conv3d_persistent_walk_across_slabs_of_other_magnitude(sa, tile, order, tuning_env):
-    """launch_bgm: cap = resident workgroups / (ceil(Cout / 32) B), at most 4 workgroups on each of 256 CUs; with at least twice as
+    """launch_conv: cap = resident workgroups / (ceil(Cout / 32) B), at most 4 workgroups on each of 256 CUs; with at least twice as
     many tiles every workgroup walks two or more (tile, tile + gridDim.x, ...), here from one depth slab into the other."""
     Cin, Cout, dhw, B = WALK
     D = dhw[0]

@@ -39,7 +39,8 @@ def _cdiv(a, b):
 
 
 def _rule(case, hint, batch=1):
-    """The launchers' fill rule (conv3d_bf16s_impl / launch_bg): stride 1 -> the tile candidate, stride 2 -> the form."""
+    """The launchers' fill rule (ss::plan_conv3d of csrc/conv_plan.h; tests/test_conv_plan.py holds this restatement to it): stride 1 -> the tile
+    candidate, stride 2 -> the form."""
     _cin, cout, (d, h, w), stride = case
     if stride == 1:
         blocks = lambda td, th: _cdiv(w, 32) * _cdiv(h, th) * _cdiv(d, td) * _cdiv(cout, 32) * batch      # noqa: E731
