@@ -1,4 +1,5 @@
-// The ONE statement of the conv launchers' tile and accumulation rule (conv3d_bf16s.hip, conv3d_gather.hip, conv3d_classifier.hip):
+// The ONE statement of the conv launchers' tile and accumulation rule (conv3d_bf16s.hip, conv3d_gather.hip, conv3d_classifier.hip)
+// and of the transposed convs' form rule (deconv3d_bf16s.hip):
 // pure functions of integers, host-only, nothing from HIP.  Callers pass ss::fill_hint() and ss::tuning() in.
 #pragma once
 #ifndef SS_S2_MS_MIN_WGS
@@ -64,4 +65,38 @@ constexpr int plan_conv2d_rows(int H, int W, int Cout, int B) {
     return blocks(1, H, W, Cout, B, 1, 16) >= kFillWgs ? 16 : (blocks(1, H, W, Cout, B, 1, 8) >= kFillWgs ? 8 : 4);
 }
 constexpr bool kConv2dAccb = SS_ACC_BLOCKED != 0;
+
+// ---- the transposed 3-D convs (deconv3d_bf16s.hip): ConvTranspose3d(k3, s2, p1, op1) over an INPUT of (D, H, W) ----
+// The tile is an input-space tile of planes x rows x 32 columns, one row per wave: 2 x 2 where the volume has two planes and
+// fewer than four rows, 1 x 4 otherwise.
+enum class DeconvTile { t2x2x32, t1x4x32 };
+// groups (fp16 form only; the bf16 forms have one form, reported as groups 0 without streaming):
+//   0: a workgroup computes all 8 output parity classes of its tile; 1: two workgroups per tile, one per class group
+//   ({0, 1, 6, 7} and {2, 3, 4, 5}); 2: two class groups + chunk-blocked accumulation.
+// stream: nontemporal stores of the output -- an instantiation of the groups-0 form only.
+struct DeconvPlan { DeconvTile tile; int groups; bool stream; };
+constexpr long long kDeconvFillUnits = 256;               // tiles x channel tiles of ONE pair from which all 8 classes share a workgroup
+constexpr long long kDeconvStreamBytes = 192LL << 20;     // output bytes of a launch from which it is streamed
+
+// forced_groups: ss::tuning().deconv_groups (SS_DECONV_GROUPS = 0 / 1 / 2, anything else: by layer size);
+// forced_stream: ss::tuning().deconv_stream (SS_DECONV_STREAM = 0 / 1, negative: by output size)
+constexpr DeconvPlan plan_deconv3d(int D, int H, int W, int Cout, int B, int nterms, int forced_groups, int forced_stream) {
+    const DeconvTile tile = (D >= 2 && H < 4) ? DeconvTile::t2x2x32 : DeconvTile::t1x4x32;
+    if (nterms != kNtermsF16) return {tile, 0, false};
+    // Parity-class groups (r05, Grp<> of the kernel), measured alone on the four transposed convs of the 1024^2 pair (hourglass2.conv6 /
+    // .conv5, hourglass_att.conv6 / .conv5; profiles/r05_f_deconv_forms.txt): all 8 classes per workgroup 128 / 55 / 38 / 39 us;
+    // two class groups at three workgroups per CU 148 / 56 / 55 / 36; two groups + chunk-blocked accumulation 163 / 75 / 55 / 36.
+    // The second staging of the input tile costs more than the third workgroup per CU returns wherever the layer fills the
+    // chip; it pays -- and brings the blocked sum's accuracy -- on a layer whose tiles number fewer than the chip's CUs.
+    // That is a property of the LAYER (tiles x channel tiles of ONE pair), so a pair gets the same bits at every batch size.
+    // SS_DECONV_GROUPS=0 / 1 / 2 forces the form (2 = groups + chunk-blocked accumulation).
+    const int td = tile == DeconvTile::t2x2x32 ? 2 : 1, th = tile == DeconvTile::t2x2x32 ? 2 : 4;
+    const long long per_pair = blocks(D, H, W, Cout, 1, td, th);
+    const int groups = (forced_groups >= 0 && forced_groups <= 2) ? forced_groups : (per_pair < kDeconvFillUnits ? 2 : 0);
+    // Nontemporal stores (STREAM of the kernel), measured r05 on hourglass2.conv6 (201 MB written, alone): 128 -> 108 us
+    // (profiles/r05_f_deconv_forms.txt).  Outputs of >= 192 MB per launch are streamed (the rule of the gwc volume kernel: smaller
+    // outputs are handed to the next kernel by the 256 MB Infinity Cache); SS_DECONV_STREAM=0/1 forces it.
+    const bool stream = forced_stream >= 0 ? forced_stream != 0 : (long long)B * Cout * 8 * D * H * W * 4 >= kDeconvStreamBytes;
+    return {tile, groups, groups == 0 && stream};
+}
 }  // namespace ss

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_plan.h"
 #include "split_f16.h"
 
 namespace {
@@ -39,8 +40,7 @@ __host__ __device__ constexpr int off_of(int s) {
 constexpr int KST = 27;           // K-steps per 16-channel chunk
 // STREAM (template argument of the kernel): the output goes out with NONTEMPORAL stores (buffer aux 2).  Measured r05 on
 // hourglass2.conv6 (201 MB written, alone): 128 -> 108 us; sc0 + nt the same; nontemporal loads of the skip tensor 119, both 124
-// (profiles/r05_f_deconv_forms.txt).  The launcher streams outputs of >= 192 MB per launch (the rule of the gwc volume kernel:
-// smaller outputs are handed to the next kernel by the 256 MB Infinity Cache); SS_DECONV_STREAM=0/1 forces it.
+// (profiles/r05_f_deconv_forms.txt).  Which launches stream: ss::plan_deconv3d (conv_plan.h).
 #ifndef SS_DECONV_XCD
 #define SS_DECONV_XCD 0           // 1: every XCD walks a contiguous eighth of the units (see the kernel's last lines)
 #endif
@@ -87,6 +87,23 @@ constexpr GroupSteps make_group_steps() {
     return t;
 }
 __device__ const GroupSteps kGroupSteps = make_group_steps();
+
+// bf16x6: the six cross products of one K-step (x = h + m + l on either side, smallest first) are summed from ZERO and join the
+// accumulator once.  Six MFMAs straight into an accumulator of magnitude |acc| round six times at ulp(|acc|) per step; a step's own
+// sum is a fraction of that, so its five inner roundings are far smaller and the accumulator takes ONE per step.  Measured on
+// (128, 64, 2, 3, 5, 64) against float64: rms error 2.76e-7 -> 0.99e-7, largest 3.99e-6 -> 1.06e-6 (profiles/deconv_forms_bf16x6_classes.txt).
+// It costs this engine 24 - 43 % on the four transposed convs of the 1024^2 pair (16 adds per step behind the MFMA pipeline, 3 - 17
+// spilled registers: profiles/deconv_forms_bf16x6_ab.txt); the default engine (f16x3) runs none of these instantiations.
+__device__ __forceinline__ f32x16 join_step6(f32x16 acc, bf16x8 ah, bf16x8 am, bf16x8 al, bf16x8 bh, bf16x8 bm, bf16x8 bl) {
+    f32x16 t = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, t, 0, 0, 0);
+    return acc + t;
+}
 
 template <int TD, int TH, int LT = 3, bool WLDS = false, int WSTEPS = 27>      // LT: operand terms kept in LDS; WLDS: + WSTEPS K-steps of a chunk's weights
 struct DB {
@@ -276,6 +293,11 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
                     const bf16x8 h8 = __builtin_bit_cast(bf16x8, make_uint4(bh[0], bh[1], bh[2], bh[3]));
                     const bf16x8 m8 = __builtin_bit_cast(bf16x8, make_uint4(bm[0], bm[1], bm[2], bm[3]));
                     const int cls = (q0 + q) * 2 + pw;
+                    if constexpr (NTERMS == 6) {      // bf16x6: the step's six products from zero, one rounding at the accumulator's magnitude
+                        const bf16x8 l8 = __builtin_bit_cast(bf16x8, make_uint4(bl[0], bl[1], bl[2], bl[3]));
+                        acc[cls] = join_step6(acc[cls], a[0], a[1], a[SNC - 1], h8, m8, l8);
+                        continue;
+                    }
                     if (SNT == 6) {
                         const bf16x8 l8 = __builtin_bit_cast(bf16x8, make_uint4(bl[0], bl[1], bl[2], bl[3]));
                         acc[cls] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], m8, acc[cls], 0, 0, 0);
@@ -462,14 +484,13 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
                     a[c] = __builtin_bit_cast(bf16x8, aq[s % AQ][c]);
                     bq[c] = __builtin_bit_cast(bf16x8, bcur[c]);
                 }
-                if (NTERMS == 6) {
-                    dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], bq[1], dst, 0, 0, 0);
-                    dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bq[NC - 1], dst, 0, 0, 0);
-                    dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[NC - 1], bq[0], dst, 0, 0, 0);
+                if constexpr (NTERMS == 6) {
+                    dst = join_step6(dst, a[0], a[1], a[NC - 1], bq[0], bq[1], bq[NC - 1]);
+                } else {
+                    dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bq[1], dst, 0, 0, 0);
+                    dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], bq[0], dst, 0, 0, 0);
+                    dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bq[0], dst, 0, 0, 0);
                 }
-                dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bq[1], dst, 0, 0, 0);
-                dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], bq[0], dst, 0, 0, 0);
-                dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bq[0], dst, 0, 0, 0);
             }
             // last tap of a run: the prefetched fragment becomes current
             if (k + 1 < NS && off_of(GP::T.step[k + 1 < NS ? k + 1 : k]) != off_of(s)) {
@@ -663,25 +684,17 @@ int launch_db(const float* in, const void* wsplit, const float* shift, const flo
 // (SHIFT27: with the skip projection only -- the one layer that has a biased 1x1x1 conv folded in has one)
 template <int TD, int TH, bool SHIFT27 = false>
 int launch_db_all(const float* in, const void* wsplit, const float* shift, const float* skip, const void* skip_wsplit,
-                  float* out, int B, int Cin, int D, int H, int W, int Cout, int Cs, int relu, int nterms, hipStream_t st) {
+                  float* out, int B, int Cin, int D, int H, int W, int Cout, int Cs, int relu, int nterms, const ss::DeconvPlan& plan,
+                  hipStream_t st) {
     // (under SHIFT27 the no-skip arms name the skip instantiation too, so none is built without the projection)
 #define SS_DB(NTERMS, HAS_SKIP) launch_db<TD, TH, NTERMS, (HAS_SKIP) || SHIFT27, false, false, false, SHIFT27>(in, wsplit, shift, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, st)
 #define SS_DF(HAS_SKIP, SPLIT, ACCB, STREAM) \
     launch_db<TD, TH, F16X3, (HAS_SKIP) || SHIFT27, SPLIT, ACCB, STREAM, SHIFT27>(in, wsplit, shift, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, st)
     if (SHIFT27 && skip == nullptr) return SS_ERR_UNSUPPORTED;
     if (nterms == F16X3) {
-        // Parity-class groups (r05, Grp<> above), measured alone on the four transposed convs of the 1024^2 pair (hourglass2.conv6 /
-        // .conv5, hourglass_att.conv6 / .conv5; profiles/r05_f_deconv_forms.txt): all 8 classes per workgroup 128 / 55 / 38 / 39 us;
-        // two class groups at three workgroups per CU 148 / 56 / 55 / 36; two groups + chunk-blocked accumulation 163 / 75 / 55 / 36.
-        // The second staging of the input tile costs more than the third workgroup per CU returns wherever the layer fills the
-        // chip; it pays -- and brings the blocked sum's accuracy -- on a layer whose tiles number fewer than the chip's CUs.
-        // That is a property of the LAYER (tiles x channel tiles of ONE pair), so a pair gets the same bits at every batch size.
-        // SS_DECONV_GROUPS=0 / 1 / 2 forces the form (2 = groups + chunk-blocked accumulation).
-        const long long per_pair = (long long)ss::ceil_div(W, 32) * ss::ceil_div(H, TH) * ss::ceil_div(D, TD) * ss::ceil_div(Cout, 32);
-        int groups = ss::tuning().deconv_groups;
-        if (groups < 0) groups = per_pair < 256 ? 2 : 0;
-        const int stream_env = ss::tuning().deconv_stream;
-        const bool stream = stream_env >= 0 ? stream_env != 0 : (long long)B * Cout * 8 * D * H * W * 4 >= (192LL << 20);
+        // which form: ss::plan_deconv3d (conv_plan.h), where the measurements behind the rule are recorded
+        const int groups = plan.groups;
+        const bool stream = plan.stream;
         if (groups == 2) return skip != nullptr ? SS_DF(true, true, true, false) : SS_DF(false, true, true, false);
         if (groups == 1) return skip != nullptr ? SS_DF(true, true, false, false) : SS_DF(false, true, false, false);
         if (stream) return skip != nullptr ? SS_DF(true, false, false, true) : SS_DF(false, false, false, true);
@@ -694,6 +707,8 @@ int launch_db_all(const float* in, const void* wsplit, const float* shift, const
 }
 
 }  // namespace
+
+static_assert(ss::kNtermsF16 == F16X3, "conv_plan.h and split_f16.h name the same engine");
 
 // The packed weights of the transposed conv (ntaps 27) and of its skip projection (ntaps 1), the one statement of their size:
 // [ceil(Cin/16)][ntaps][3 bf16 or 2 fp16 terms][2 channel halves][Cout][8] two-byte terms, then (fp16 form) float[Cout].
@@ -746,9 +761,10 @@ extern "C" int ss_deconv3d_bf16s_fwd(const float* in, const void* wsplit, const 
     if (skip != nullptr && (long long)Cs * 8 * D * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
     if ((long long)Cout * 8 * D * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;       // 32-bit output offsets per batch element
     hipStream_t st = ss::as_stream(stream);
-    if (D >= 2 && H < 4)
-        return launch_db_all<2, 2>(in, wsplit, shift, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, nterms, st);
-    return launch_db_all<1, 4>(in, wsplit, shift, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, nterms, st);
+    const ss::DeconvPlan plan = ss::plan_deconv3d(D, H, W, Cout, B, nterms, ss::tuning().deconv_groups, ss::tuning().deconv_stream);
+    if (plan.tile == ss::DeconvTile::t2x2x32)
+        return launch_db_all<2, 2>(in, wsplit, shift, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, nterms, plan, st);
+    return launch_db_all<1, 4>(in, wsplit, shift, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, nterms, plan, st);
 }
 
 // ... with the shift as a table over the 27 border cases of an output position (SHIFT27 above): shift27 [27][Cout]
@@ -763,7 +779,8 @@ extern "C" int ss_deconv3d_bf16s_shift27_fwd(const float* in, const void* wsplit
     if ((long long)Cs * 8 * D * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
     if ((long long)Cout * 8 * D * H * W * 4 >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
     hipStream_t st = ss::as_stream(stream);
-    if (D >= 2 && H < 4)
-        return launch_db_all<2, 2, true>(in, wsplit, shift27, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, nterms, st);
-    return launch_db_all<1, 4, true>(in, wsplit, shift27, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, nterms, st);
+    const ss::DeconvPlan plan = ss::plan_deconv3d(D, H, W, Cout, B, nterms, ss::tuning().deconv_groups, ss::tuning().deconv_stream);
+    if (plan.tile == ss::DeconvTile::t2x2x32)
+        return launch_db_all<2, 2, true>(in, wsplit, shift27, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, nterms, plan, st);
+    return launch_db_all<1, 4, true>(in, wsplit, shift27, skip, skip_wsplit, out, B, Cin, D, H, W, Cout, Cs, relu, nterms, plan, st);
 }

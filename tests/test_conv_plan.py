@@ -5,7 +5,10 @@ header is compiled with the system c++ and called through ctypes.
     fill hint or a forced tile;
   * the Python restatements of the rule in the GPU tests (_rule of tests/test_fill_hint_gpu.py; _s1_form, _s2_form, _stem_form,
     _conv2d_tile of tests/test_f16_ranges_gpu.py) and engine.classifier_fused_applies give the header's answers;
-  * both sides of every threshold, the forced tile, the depth rule of the 4-row tile, one plan for the plain and the gather entry.
+  * both sides of every threshold, the forced tile, the depth rule of the 4-row tile, one plan for the plain and the gather entry;
+  * the transposed convs' form rule (ss::plan_deconv3d, what deconv3d_bf16s.hip launches by): its restatement _deconv_form of
+    tests/test_f16_ranges_gpu.py on a grid across every threshold and every value of SS_DECONV_GROUPS and SS_DECONV_STREAM, and the
+    forms of the four transposed convs of the 1024^2 pair.
 """
 import ctypes
 import itertools
@@ -30,6 +33,11 @@ void probe_plan3d(int Do, int Ho, int Wo, int Cout, int B, int stride, int nterm
 int probe_rows2d(int H, int W, int Cout, int B) { return ss::plan_conv2d_rows(H, W, Cout, B); }
 int probe_small_layer(int D, int H, int W, int Cout) { return ss::small_layer(D, H, W, Cout); }
 int probe_s2_min_wgs() { return SS_S2_MS_MIN_WGS; }
+void probe_deconv3d(int D, int H, int W, int Cout, int B, int nterms, int forced_groups, int forced_stream, int* out) {
+    const ss::DeconvPlan p = ss::plan_deconv3d(D, H, W, Cout, B, nterms, forced_groups, forced_stream);
+    out[0] = p.tile == ss::DeconvTile::t2x2x32 ? 2 : 1; out[1] = p.tile == ss::DeconvTile::t2x2x32 ? 2 : 4; out[2] = p.groups; out[3] = p.stream;
+}
+long long probe_deconv_stream_bytes() { return ss::kDeconvStreamBytes; }
 }
 """
 TILES = ("4x4x32", "2x8x32", "1x8x32", "1x4x32")          # enum Tile3
@@ -46,6 +54,7 @@ def probe(tmp_path_factory):
     subprocess.check_call(["c++", "-std=c++17", "-O1", "-Wall", "-Werror", "-shared", "-fPIC", "-I", CSRC, str(src), "-o", str(so)])
     lib = ctypes.CDLL(str(so))
     lib.probe_blocks.restype = ctypes.c_longlong
+    lib.probe_deconv_stream_bytes.restype = ctypes.c_longlong
     return lib
 
 
@@ -168,3 +177,89 @@ def test_classifier_rule_is_the_engines_arithmetic(probe):
         assert want == (not probe.probe_small_layer(D, H, W, 32)), (B, D, H, W)
         served.append(want)
     assert served[:10] == [True] * 6 + [False, False, True, True] and not any(served[10:])
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# the transposed convs: ss::plan_deconv3d
+# --------------------------------------------------------------------------------------------------------------------
+
+def deconv_plan(lib, D, H, W, cout, B=1, nterms=19, groups=-1, stream=-1):
+    """-> ((planes, rows) of the tile, groups, stream), the form of fr._deconv_form's answer"""
+    r = (ctypes.c_int * 4)()
+    lib.probe_deconv3d(D, H, W, cout, B, nterms, groups, stream, r)
+    return (r[0], r[1]), r[2], bool(r[3])
+
+
+def _per_pair(D, H, W, cout):
+    (td, th), _, _ = fr._deconv_form(D, H, W, cout)
+    return fr._cdiv(W, 32) * fr._cdiv(H, th) * fr._cdiv(D, td) * fr._cdiv(cout, 32)
+
+
+# (D, H, W, Cout, B) either side of each threshold.  per_pair = 255 | 256: 1 x 4 tile 5 x 17 x 3 tiles x 1 | 4 x 16 x 4 x 1 (and by the
+# channel tiles: 1 x 5 x 17 x 3 | 2 x 16 x 4 x 2), 2 x 2 tile (H < 4, D >= 2) 17 x 1 x 15 x 1 | 16 x 2 x 8 x 1 (and 17 x 1 x 3 x 5 | 16 x 1 x 16 x 1); H = 3 | 4 and D = 1 | 2 move the tile;
+# the output, B Cout 8 D H W 4 bytes: 192 MB = 2^21 x 96, so Cout 32 x D 12 x H 128 x W 128 is AT it, W = 127 below, and B counts
+DECONV_EDGES = [(5, 68, 96, 32, 1), (4, 64, 128, 32, 1), (17, 20, 32, 96, 1), (4, 64, 64, 64, 1), (4, 64, 64, 33, 1),
+                (30, 2, 17 * 32, 32, 1), (16, 3, 16 * 32, 32, 1), (32, 2, 16 * 32 - 31, 32, 1), (6, 2, 17 * 32, 160, 1),
+                (2, 3, 64, 32, 1), (2, 4, 64, 32, 1), (1, 3, 64, 32, 1), (1, 4, 64, 32, 1), (3, 1, 5, 8, 2), (1, 1, 1, 1, 1),
+                (12, 128, 128, 32, 1), (12, 128, 127, 32, 1), (6, 128, 128, 32, 2), (6, 128, 127, 32, 2), (12, 128, 128, 31, 1),
+                (6, 128, 128, 32, 1), (3, 128, 128, 32, 4), (3, 128, 128, 32, 3), (8, 32, 32, 64, 12), (8, 32, 32, 64, 11)]
+
+
+def test_deconv_restatement_gives_the_headers_answers(probe):
+    shapes = list(DECONV_EDGES)
+    shapes += [(D, H, W, cout, B) for D, H, W, cout, B in itertools.product((1, 2, 3, 16), (1, 3, 4, 9, 64), (1, 33, 64, 512), (1, 32, 33, 64, 128), (1, 2))]
+    for (D, H, W, cout, B), nterms, groups, stream in itertools.product(shapes, (19, 6, 3), (-1, 0, 1, 2, 3), (-1, 0, 1)):
+        assert deconv_plan(probe, D, H, W, cout, B, nterms, groups, stream) == fr._deconv_form(D, H, W, cout, B, nterms, groups, stream), \
+            (D, H, W, cout, B, nterms, groups, stream)
+
+
+def test_deconv_both_sides_of_every_threshold(probe):
+    # per_pair 255 | 256, each tile: groups 2 | 0, at every batch size (the LAYER's property) and whatever the stream switch says
+    for below, at, tile in (((5, 68, 96, 32), (4, 64, 128, 32), (1, 4)), ((17, 20, 32, 96), (4, 64, 64, 64), (1, 4)),
+                            ((30, 2, 17 * 32, 32), (16, 3, 16 * 32, 32), (2, 2)), ((6, 2, 17 * 32, 160), (32, 2, 16 * 32 - 31, 32), (2, 2))):
+        assert (_per_pair(*below), _per_pair(*at)) == (255, 256)
+        for B, stream in ((1, -1), (2, -1), (1, 0), (2, 0), (8, 0)):         # (at B = 8 the larger of these would stream by its size)
+            assert deconv_plan(probe, *below, B, stream=stream) == (tile, 2, False) and deconv_plan(probe, *at, B, stream=stream) == (tile, 0, False)
+        assert deconv_plan(probe, *at, 1, stream=1) == (tile, 0, True) and deconv_plan(probe, *below, 1, stream=1) == (tile, 2, False)
+    assert deconv_plan(probe, 4, 64, 64, 33)[1] == 0 and deconv_plan(probe, 4, 64, 64, 32)[1] == 2      # 128 tiles: the 33rd channel opens a second channel tile
+    # the tile: 2 x 2 needs two planes AND fewer than four rows
+    assert [deconv_plan(probe, D, H, 64, 32)[0] for D, H in ((2, 3), (2, 4), (1, 3), (1, 4), (3, 1), (1, 1))] == [(2, 2), (1, 4), (1, 4), (1, 4), (2, 2), (1, 4)]
+    # output bytes, integers only: B x Cout x 8 D H W x 4 at 192 MB | one column less
+    edge = probe.probe_deconv_stream_bytes()
+    assert edge == 192 << 20
+    for (D, H, W, cout, B), streams in (((12, 128, 128, 32, 1), True), ((12, 128, 127, 32, 1), False), ((6, 128, 128, 32, 2), True),
+                                        ((6, 128, 127, 32, 2), False), ((6, 128, 128, 32, 1), False), ((3, 128, 128, 32, 4), True),
+                                        ((3, 128, 128, 32, 3), False), ((12, 128, 128, 31, 1), False)):
+        nbytes = B * cout * 8 * D * H * W * 4
+        assert (nbytes >= edge) == streams and (B * cout * D * H * W != 32 * 12 * 128 * 128 or nbytes == edge)
+        assert _per_pair(D, H, W, cout) >= 256
+        assert deconv_plan(probe, D, H, W, cout, B) == ((1, 4), 0, streams)
+        assert deconv_plan(probe, D, H, W, cout, B, stream=0)[2] is False and deconv_plan(probe, D, H, W, cout, B, stream=1)[2] is True
+    # a streamed size on the two-group forms: they have no streaming instantiation
+    assert _per_pair(8, 32, 32, 64) == 128 and 12 * 64 * 8 * 8 * 32 * 32 * 4 == edge
+    assert deconv_plan(probe, 8, 32, 32, 64, 12) == ((1, 4), 2, False) and deconv_plan(probe, 8, 32, 32, 64, 12, groups=1) == ((1, 4), 1, False)
+    assert deconv_plan(probe, 8, 32, 32, 64, 12, groups=0) == ((1, 4), 0, True) and deconv_plan(probe, 8, 32, 32, 64, 11, groups=0) == ((1, 4), 0, False)
+    # every forced value of both switches, on a layer either side of the count; 3 and beyond: as unset
+    for shape, natural in (((2, 3, 5, 64), 2), ((16, 32, 64, 32), 0)):
+        assert _per_pair(*shape) < 256 if natural == 2 else _per_pair(*shape) >= 256
+        for groups, stream in itertools.product((-1, 0, 1, 2, 3), (-1, 0, 1)):
+            want = groups if groups in (0, 1, 2) else natural
+            assert deconv_plan(probe, *shape, 1, groups=groups, stream=stream)[1:] == (want, want == 0 and stream == 1)
+        for nterms in (6, 3):               # the bf16 forms: one form, no switch
+            assert {deconv_plan(probe, *shape, 1, nterms, g, s)[1:] for g, s in itertools.product((-1, 0, 1, 2), (-1, 0, 1))} == {(0, False)}
+
+
+def test_deconv_forms_of_the_1024_pair(probe):
+    """the four transposed convs of the 1024^2 / maxdisp 128 pair (input D, H, W, Cout; tools/run_kernel.py builds the same): all 8
+    classes per workgroup wherever the layer fills the chip, hourglass2.conv6 streamed (192 MB written at batch 1), the 128-unit
+    hourglass_att.conv5 on two class groups with chunk-blocked accumulation -- at every batch size"""
+    layers = {"hourglass2.conv6": ((12, 128, 128, 32), 1536, 0), "hourglass2.conv5": ((6, 64, 64, 64), 384, 0),
+              "hourglass_att.conv6": ((16, 64, 64, 32), 512, 0), "hourglass_att.conv5": ((8, 32, 32, 64), 128, 2)}
+    for name, (shape, units, groups) in layers.items():
+        assert _per_pair(*shape) == units, name
+        for B in (1, 2, 4):
+            D, H, W, cout = shape
+            streams = groups == 0 and B * cout * 8 * D * H * W * 4 >= 192 << 20
+            assert deconv_plan(probe, *shape, B) == ((1, 4), groups, streams), (name, B)
+    assert deconv_plan(probe, 12, 128, 128, 32, 1)[2] and not deconv_plan(probe, 6, 64, 64, 64, 1)[2]
+    assert deconv_plan(probe, 6, 64, 64, 64, 4)[2] and not deconv_plan(probe, 8, 32, 32, 64, 64)[2]

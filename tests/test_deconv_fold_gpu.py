@@ -7,7 +7,8 @@ the 64-channel skip tensor to relu(bn(conv5(final1x1(y))) + bn(redir2(skip))), u
   * the folded path (ONE launch) must be as close to float64 as today's two launches (pointwise_bf16s, deconv3d_bf16s) on the
     same input: error <= 1.5 x theirs + 1e-6 (the margin of test_parity_gpu.test_deconv3d_split_bf16_engine for two roundings of
     the same size), SEPARATELY on the border set (the last odd plane, row and column: cases 2 of the shift table) and on the
-    interior, so that a wrong table entry cannot hide in the mean;
+    interior, so that a wrong table entry cannot hide in the mean -- on the fp16 engine under every form of the kernel: what the
+    launcher picks at this size, SS_DECONV_GROUPS = 0 / 1 / 2, and groups 0 with nontemporal stores (SS_DECONV_STREAM=1);
   * HotSegment at the s128 fixture with SS_ATTN_FOLD 0 and 1: the same candidates, `pred` / `pred_att` within the bounds of
     test_parity_gpu.test_hot_segment_with_hip_2d_convs.
 Every figure is printed; SS_ATTN_FOLD_ERR_OUT=<file> keeps the table (profiles/attn_fold_err.txt is a copy of one run).
@@ -89,7 +90,7 @@ def _bn64(bn, t):
 # (2, 3, 5): the kernel's 2 x 2-row tile, taken where H < 4 and D >= 2; bf16x6: the table in the kernel's three-bf16-term form
 @pytest.mark.parametrize("engine,shape", [("f16x3", (2, 5, 37)), ("f16x3", (1, 3, 6)), ("f16x3", (2, 3, 5)), ("bf16x6", (2, 5, 37)),
                                           ("bf16x6", (2, 3, 5))], indirect=["engine"])
-def test_conv5_with_final1x1_folded(sa, engine, shape):
+def test_conv5_with_final1x1_folded(sa, engine, shape, tuning_env):
     D, H, W = shape
     hg = _hourglass(sa)
     y = dd.t_normalish((2, 128, D, H, W), 911)
@@ -102,25 +103,32 @@ def test_conv5_with_final1x1_folded(sa, engine, shape):
     hg = hg.cuda()
     yd, sd = y.cuda(), skip.cuda()
     M = sa.modules
-    with torch.no_grad():
-        assert hg._up_takes_split_engine("u5", hg.conv5, hg.redir2, yd) and M._deconv_nterms() == (19 if engine == "f16x3" else 6)
-        _, _, wo, bo, bf = hg.attention_block._params_split()
-        assert bf
-        two = hg._up("u5", hg.conv5, hg.redir2, M.conv3d_pointwise_bf16s_hip(yd, wo, 128, None, bo, False, M._aux_nterms()), sd)
-        one = hg._up5_folded(yd, sd)
-    torch.cuda.synchronize()
-    assert one.shape == two.shape == ref.shape and bool(torch.isfinite(one).all())
     border = torch.zeros(ref.shape[2:], dtype=torch.bool)
     border[2 * D - 1], border[:, 2 * H - 1], border[:, :, 2 * W - 1] = True, True, True
-    e_one, e_two = (one.double().cpu() - ref).abs(), (two.double().cpu() - ref).abs()
-    for name, mask in (("border", border), ("interior", ~border)):
-        a, b = float(e_one[:, :, mask].max()), float(e_two[:, :, mask].max())
-        _record(f"conv5 fold {engine} {shape} {name:8s} ({int(mask.sum())} positions): folded {a:.3e}  two launches {b:.3e}  max|ref| {float(ref.abs().max()):.3g}")
-        assert a <= 1.5 * b + 1e-6, (name, a, b)
-    # the same bits for batch element 1 alone
-    with torch.no_grad():
-        alone = hg._up5_folded(yd[1:2].contiguous(), sd[1:2].contiguous())
-    assert torch.equal(alone[0], one[1])
+    # (SS_DECONV_GROUPS, SS_DECONV_STREAM) of the SHIFT27 instantiations; the bf16 engine has one form
+    forms = [(None, None)] + ([("0", "0"), ("0", "1"), ("1", None), ("2", None)] if engine == "f16x3" else [])
+    for groups, stream in forms:
+        if groups is not None:
+            tuning_env("SS_DECONV_GROUPS", groups)
+            tuning_env("SS_DECONV_STREAM", stream or "-1")
+        form = "" if groups is None else f" groups {groups}" + (" stream" if stream == "1" else "")
+        with torch.no_grad():
+            assert hg._up_takes_split_engine("u5", hg.conv5, hg.redir2, yd) and M._deconv_nterms() == (19 if engine == "f16x3" else 6)
+            _, _, wo, bo, bf = hg.attention_block._params_split()
+            assert bf
+            two = hg._up("u5", hg.conv5, hg.redir2, M.conv3d_pointwise_bf16s_hip(yd, wo, 128, None, bo, False, M._aux_nterms()), sd)
+            one = hg._up5_folded(yd, sd)
+        torch.cuda.synchronize()
+        assert one.shape == two.shape == ref.shape and bool(torch.isfinite(one).all())
+        e_one, e_two = (one.double().cpu() - ref).abs(), (two.double().cpu() - ref).abs()
+        for name, mask in (("border", border), ("interior", ~border)):
+            a, b = float(e_one[:, :, mask].max()), float(e_two[:, :, mask].max())
+            _record(f"conv5 fold {engine}{form} {shape} {name:8s} ({int(mask.sum())} positions): folded {a:.3e}  two launches {b:.3e}  max|ref| {float(ref.abs().max()):.3g}")
+            assert a <= 1.5 * b + 1e-6, (form, name, a, b)
+        # the same bits for batch element 1 alone
+        with torch.no_grad():
+            alone = hg._up5_folded(yd[1:2].contiguous(), sd[1:2].contiguous())
+        assert torch.equal(alone[0], one[1]), form
 
 
 def test_hot_segment_fold_on_and_off(sa, golden):

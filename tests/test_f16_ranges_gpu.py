@@ -512,28 +512,64 @@ def test_conv3d_persistent_walk_across_slabs_of_other_magnitude(sa, tile, order,
 DECONV3D = (48, 40, 3, 9, 35, 16)       # the shape of test_deconv3d_f16_form_block_floating_ranges
 
 
-@pytest.mark.parametrize("split", ["0", "1"])
+def _deconv_form(D, H, W, Cout, B=1, nterms=19, groups=-1, stream=-1):
+    """ss::plan_deconv3d (csrc/conv_plan.h) over an INPUT of (D, H, W): -> ((planes, rows) of the 32-column tile, groups, stream).
+    groups 0: all 8 output parity classes in one workgroup, 1: two class groups, 2: two groups + chunk-blocked accumulation -- by
+    what ONE pair offers the chip, or SS_DECONV_GROUPS; stream: nontemporal stores (groups 0 only), by the launch's output bytes or
+    SS_DECONV_STREAM.  The bf16 forms have one form: (tile, 0, False)."""
+    td, th = (2, 2) if D >= 2 and H < 4 else (1, 4)
+    if nterms != 19:
+        return (td, th), 0, False
+    per_pair = _cdiv(W, 32) * _cdiv(H, th) * _cdiv(D, td) * _cdiv(Cout, 32)
+    g = groups if groups in (0, 1, 2) else (2 if per_pair < 256 else 0)
+    s = stream != 0 if stream >= 0 else B * Cout * 8 * D * H * W * 4 >= 192 << 20
+    return (td, th), g, g == 0 and s
+
+
+def _deconv_skip_orders(D, H, W, Cout):
+    """the non-split forms project the skip tensor before the main loop where (unit ^ channel tile) is odd, after it elsewhere:
+    -> the set of (unit ^ channel tile) & 1 over a launch's workgroups ({0, 1}: both orders run)"""
+    (td, th), _, _ = _deconv_form(D, H, W, Cout)
+    units = _cdiv(W, 32) * _cdiv(H, th) * _cdiv(D, td)
+    return {(u ^ c) & 1 for u in range(units) for c in range(_cdiv(Cout, 32))}
+
+
+def test_deconv3d_range_shape_runs_both_skip_orders():
+    _cin, Cout, D, H, W, _cs = DECONV3D
+    assert _deconv_form(D, H, W, Cout) == ((1, 4), 2, False)        # 2 x 3 x 3 tiles of 1 x 4 x 32, 2 channel tiles: 36 < 256
+    assert (_cdiv(W, 32), _cdiv(H, 4), D, _cdiv(Cout, 32)) == (2, 3, 3, 2) and _deconv_skip_orders(D, H, W, Cout) == {0, 1}
+
+
+@pytest.mark.parametrize("split", ["0", "1"])     # (SS_DECONV_SPLIT: the form of the exact-fp32 kernel that is the yardstick)
 @pytest.mark.parametrize("skip_mul", [1e-6, 1.0, 1e6])
-@pytest.mark.parametrize("name", CHANNEL)
+@pytest.mark.parametrize("name", CHANNEL + ["out_channels_1e-8_to_1e+8"])
 def test_deconv3d_ranges_beside_the_skip_projection(sa, name, skip_mul, split, tuning_env):
     """the fp16 main loop with a growing / shrinking maximum, and the bf16 skip projection that initialises its accumulators
-    (E_INIT_SHIFT) 12 decades below, at and 12 decades above the main term"""
+    (E_INIT_SHIFT: SS_DECONV_GROUPS=0, the workgroups with (unit ^ channel tile) odd) or joins them after the loop (the other
+    workgroups, and all of groups 1 and 2), 12 decades below, at and 12 decades above the main term; the weights of both, per
+    output channel, times the case's multipliers"""
     tuning_env("SS_DECONV_SPLIT", split)
     M = sa.modules
     Cin, Cout, D, H, W, Cs = DECONV3D
-    x, _ = _range_input(name, (1, Cin, D, H, W), 5400, Cout)
+    x, w_mul = _range_input(name, (1, Cin, D, H, W), 5400, Cout)
     g = _gen(5401)
     w = (torch.rand(Cin, Cout, 3, 3, 3, generator=g) * 2 - 1) * (3.0 / (Cin * 27 / 8)) ** 0.5
     ws = (torch.rand(Cout, Cs, 1, 1, 1, generator=g) * 2 - 1) * (3.0 / Cs) ** 0.5
+    w = (w.double() * w_mul.reshape(1, -1, 1, 1, 1)).float()            # a transposed conv's weight is [Cin, Cout, ...]
+    ws = (ws.double() * w_mul.reshape(-1, 1, 1, 1, 1)).float()
     main = F.conv_transpose3d(x.double(), w.double(), None, stride=2, padding=1, output_padding=1)
-    skip = (torch.randn(1, Cs, 2 * D, 2 * H, 2 * W, generator=g).double() * float(main.pow(2).mean().sqrt()) * skip_mul).float()
+    main_rms = float((main / w_mul.reshape(1, -1, 1, 1, 1)).pow(2).mean().sqrt())      # of the main term before the channels' multipliers
+    skip = (torch.randn(1, Cs, 2 * D, 2 * H, 2 * W, generator=g).double() * main_rms * skip_mul).float()
     ref = main + F.conv3d(skip.double(), ws.double())
     wp = M.pack_conv_weight(w.cuda(), transposed=True)
     wsp = M.pack_conv_weight(ws.cuda()).reshape(Cs, Cout).contiguous()
     zero = torch.zeros(Cout).cuda()
-    y = M.deconv3d_bf16s_hip(x.cuda(), M.pack_deconv_weight_bf16s(wp, 19), Cout, zero, False, 19, skip.cuda(), M.pack_deconv_weight_bf16s(wsp))
     y32 = M.deconv3d_hip(x.cuda(), wp, zero, False, skip.cuda(), wsp)
-    _judge32(f"deconv3d split {split} {name} skip x{skip_mul:g}", y, y32, ref)
+    for groups in (0, 1, 2):
+        tuning_env("SS_DECONV_GROUPS", str(groups))
+        assert _deconv_form(D, H, W, Cout, groups=groups)[1] == groups
+        y = M.deconv3d_bf16s_hip(x.cuda(), M.pack_deconv_weight_bf16s(wp, 19), Cout, zero, False, 19, skip.cuda(), M.pack_deconv_weight_bf16s(wsp))
+        _judge32(f"deconv3d groups {groups} split {split} {name} skip x{skip_mul:g}", y, y32, ref)
 
 
 # ---- the gathered stem ----

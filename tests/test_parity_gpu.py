@@ -1321,8 +1321,10 @@ def test_conv3d_f16_form_block_floating_ranges(sa, name, stride):
 
 
 @pytest.mark.parametrize("in_mul", [1e-6, 1.0, 1e6])
-def test_deconv3d_f16_form_block_floating_ranges(sa, in_mul):
-    """the transposed conv's fp16 main loop beside its bf16 skip projection of O(1) values, the two 12 decades apart"""
+def test_deconv3d_f16_form_block_floating_ranges(sa, in_mul, tuning_env):
+    """the transposed conv's fp16 main loop beside its bf16 skip projection of O(1) values, the two 12 decades apart: under the
+    form this small layer gets (two class groups + chunk-blocked accumulation, the skip projection after the main loop) and under
+    the form of the large layers (SS_DECONV_GROUPS=0: all 8 classes per workgroup, the skip projection FIRST in every other one)"""
     import torch.nn.functional as F
     from oracle import detdata as dd
     Cin, Cout, D, H, W, Cs = 48, 40, 3, 9, 35, 16
@@ -1334,13 +1336,17 @@ def test_deconv3d_f16_form_block_floating_ranges(sa, in_mul):
     wp = sa.modules.pack_conv_weight(dev(w), transposed=True)
     wsp = sa.modules.pack_conv_weight(dev(ws)).reshape(Cs, Cout).contiguous()
     zero = dev(torch.zeros(Cout))
-    y = sa.modules.deconv3d_bf16s_hip(dev(x), sa.modules.pack_deconv_weight_bf16s(wp, 19), Cout, zero, False, 19, dev(skip),
-                                      sa.modules.pack_deconv_weight_bf16s(wsp))
     y32 = sa.modules.deconv3d_hip(dev(x), wp, zero, False, dev(skip), wsp)
     rms = float(ref.pow(2).mean().sqrt())
-    e, e32 = float((y.double().cpu() - ref).abs().max()) / rms, float((y32.double().cpu() - ref).abs().max()) / rms
-    REPORT[f"deconv3d_f16x3_range/{in_mul}"] = e
-    assert e <= 1.5 * e32 + 1e-6, (e, e32)
+    e32 = float((y32.double().cpu() - ref).abs().max()) / rms
+    for groups in (None, 0, 2):             # None: no switch, what the launcher picks (groups 2 at this size)
+        if groups is not None:
+            tuning_env("SS_DECONV_GROUPS", str(groups))
+        y = sa.modules.deconv3d_bf16s_hip(dev(x), sa.modules.pack_deconv_weight_bf16s(wp, 19), Cout, zero, False, 19, dev(skip),
+                                          sa.modules.pack_deconv_weight_bf16s(wsp))
+        e = float((y.double().cpu() - ref).abs().max()) / rms
+        REPORT[f"deconv3d_f16x3_range/{in_mul}" + ("" if groups is None else f"/groups{groups}")] = e
+        assert e <= 1.5 * e32 + 1e-6, (groups, e, e32)
 
 
 def test_patch_and_gate_fusion(sa):
@@ -1971,6 +1977,41 @@ def test_deconv3d_training_forward_dgrad_wgrad_in_hip(sa, case):
     e_w = float((dc.weight.grad.double().cpu() - w64.grad).abs().max()) / scale(w64.grad)
     REPORT[f"deconv3d_train/{case}"] = (e_y, e_x, e_w)
     assert e_y <= 2e-6 and e_x <= 2e-6 and e_w <= 5e-6, (e_y, e_x, e_w)
+
+
+@pytest.fixture
+def counted_bf16s_deconv(sa, monkeypatch):
+    """training's transposed conv (train_layers._deconv_k3_forward) takes the bf16s kernel at any size; -> the shapes it was given"""
+    calls = []
+    inner = sa.train_layers.deconv3d_bf16s_hip
+
+    def counted(x, *a, **k):
+        calls.append(tuple(x.shape))
+        return inner(x, *a, **k)
+    monkeypatch.setattr(sa.engine, "DECONV_MIN_WORKGROUPS", 0)
+    monkeypatch.setattr(sa.engine, "DECONV_BF16S", True)
+    monkeypatch.setattr(sa.train_layers, "deconv3d_bf16s_hip", counted)
+    return calls
+
+
+@pytest.mark.parametrize("groups", ["0", "1"])
+def test_deconv3d_training_in_the_forms_of_large_layers(sa, groups, tuning_env, counted_bf16s_deconv):
+    """test_deconv3d_training_forward_dgrad_wgrad_in_hip's first case with the forward on the forms a full-size layer gets
+    (SS_DECONV_GROUPS=0: all 8 parity classes per workgroup; 1: two class groups), no skip tensor and a zero shift"""
+    assert sa.engine._deconv_nterms() == 19, "the class groups are forms of the fp16 engine"
+    tuning_env("SS_DECONV_GROUPS", groups)
+    test_deconv3d_training_forward_dgrad_wgrad_in_hip(sa, (1, 64, 32, 3, 6, 18))
+    assert counted_bf16s_deconv == [(1, 64, 3, 6, 18)]
+
+
+@pytest.mark.parametrize("groups", ["0", "1"])
+def test_conv3d_stride2_data_gradient_in_the_forms_of_large_layers(sa, groups, tuning_env, counted_bf16s_deconv):
+    """the stride-2 case (1, 32, 64, 6, 8, 34, 2) of CONV_TRAIN_CASES: its data gradient is the transposed conv of the output
+    gradient [1, 64, 3, 4, 17], run here on the forms a full-size layer gets"""
+    assert sa.engine._deconv_nterms() == 19, "the class groups are forms of the fp16 engine"
+    tuning_env("SS_DECONV_GROUPS", groups)
+    test_conv3d_training_forward_dgrad_wgrad_in_hip(sa, (1, 32, 64, 6, 8, 34, 2))
+    assert counted_bf16s_deconv == [(1, 64, 3, 4, 17)]
 
 
 def _rel(a, ref):
