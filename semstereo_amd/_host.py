@@ -33,5 +33,30 @@ def _const(key, device, make):
     return _CONST[k]
 
 
+def _label_classes(y, C):
+    """int64 of y's shape: the class of a label in [0, C), or C for "outside" -- csrc/metrics_decode.h's label_class.  Float labels
+    truncate toward zero, NaN is outside."""
+    if y.is_floating_point():
+        inside = (y > -1) & (y < C)
+        y = torch.where(inside, y, torch.zeros_like(y)).long()
+    else:
+        y = y.long()
+        inside = (y >= 0) & (y < C)
+    return torch.where(inside, y, torch.full_like(y, C))
+
+
+def argmax_first(logits):
+    """np.argmax over the channel axis as elementwise selects: the lowest index among equal maxima, a NaN counts as the maximum
+    (csrc/metrics_decode.h's argmax_take)."""
+    best = logits[:, 0]
+    idx = torch.zeros(best.shape, dtype=torch.int64, device=logits.device)
+    for k in range(1, logits.shape[1]):
+        z = logits[:, k]
+        take = ~torch.isnan(best) & ((z > best) | torch.isnan(z))
+        best = torch.where(take, z, best)
+        idx = torch.where(take, torch.full_like(idx, k), idx)
+    return idx
+
+
 def bn_ok(bn):
     return isinstance(bn, nn.BatchNorm2d) and (bn.training or bn.running_mean is not None)

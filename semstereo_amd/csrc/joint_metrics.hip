@@ -1,7 +1,8 @@
 // The joint stereo-semantic record of one batch: disparity error per semantic class and the confusion matrix gated by the disparity
 // error (mIoU-3), from ONE pass over the tensors eval_metrics reads -- up to four estimates, the ground truth, the mask (or its range),
-// the six logits and the label map.  A streaming reduction in the style of metrics.hip: 256 threads, grid (G, B) with a grid-stride
-// loop per image, four pixels of a row per thread and trip, 16-byte loads where width and alignment allow.
+// the six logits and the label map.  A streaming reduction of the stream.h family on a grid (G, B), image blockIdx.y, which keeps
+// summation orders of its own: the histogram columns and the per-class sums below are not the shape of stream.h's block_sum, and
+// their order is part of the recorded bits.
 //
 // Where the numbers live (profiles/EXPERIMENTS.md section U):
 //   every integer count   a histogram in LDS, hist[bin][column], column = lane & 31, added to with a ds_add_u32 that returns nothing.
@@ -11,15 +12,16 @@
 //                         sum of fp32 values in double is the only form whose error stays at the 2^-53 per term that the record's
 //                         consumers are checked against.  7 x n_est doubles: 56 VGPRs at four estimates, no scratch.
 // Each workgroup leaves one partial (doubles, then 32-bit counts) in the caller's workspace; a second launch adds the partials in a fixed
-// order.  No floating-point atomics: two calls give the same bits.  Nothing allocates, copies, synchronises or returns to the host.
+// order.  Nothing allocates, copies, synchronises or returns to the host.
 #include "common.h"
 #include "metrics_decode.h"
+#include "stream.h"
 
 namespace {
 
 using namespace ss::metrics;
+using namespace ss::stream;    // BLOCK, grid_for, aligned_to, aligned16, wave_sum
 
-constexpr int BLOCK = 256;
 constexpr int COLS = 32;       // columns of a histogram bin
 constexpr int GJ = 1024;       // workgroups of the reduction, all images together: image b gets GJ / B of them at most ...
 constexpr int GI = 512;        // ... and never more than this: two per CU, and half the partials for the finish to read (section U)
@@ -130,13 +132,13 @@ __global__ __launch_bounds__(BLOCK) void joint_metrics_k(JointArgs a) {
     const unsigned char* mask = a.mask ? a.mask + base : nullptr;
     const float* z = a.z ? a.z + base * NC : nullptr;
     const float* est[NE];
-    bool vec = (a.W & 3) == 0 && aligned16(gt) && (!mask || (reinterpret_cast<uintptr_t>(mask) & 3) == 0) && (!z || aligned16(z));
+    bool vec = (a.W & 3) == 0 && aligned16(gt) && aligned_to(mask, 4) && (!z || aligned16(z));
 #pragma unroll
     for (int k = 0; k < NE; ++k) {
         est[k] = a.est[k] + base;
         vec = vec && aligned16(est[k]);
     }
-    const bool ywide = ((a.y_row | a.y_img) & 3) == 0 && (reinterpret_cast<uintptr_t>(a.y) & (LT == LT_U8 ? 3 : 15)) == 0;
+    const bool ywide = ((a.y_row | a.y_img) & 3) == 0 && aligned_to(a.y, LT == LT_U8 ? 4 : 16);
     const long long ybase = (long long)b * a.y_img;
     const int stride = gridDim.x * BLOCK, first = blockIdx.x * BLOCK + tid;
     const int n4 = vec ? n / 4 : 0;                            // (W % 4 == 0: four pixels of a load share a row, and n4 * 4 == n)
@@ -314,9 +316,7 @@ extern "C" int ss_joint_metrics_fwd(const float* est0, const float* est1, const 
         if (i >= n_thr) a.thr[i] = inf;
     }
     if (num_classes != NC || B > GJ || (long long)H * W >= 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
-    const long long n = (long long)H * W;
-    const long long g = ss::ceil_div_ll(ss::ceil_div_ll(n, 4), BLOCK);
-    const int cap = GJ / B < GI ? GJ / B : GI, G = (int)(g < cap ? g : cap);
+    const int G = grid_for(ss::ceil_div_ll((long long)H * W, 4), GJ / B < GI ? GJ / B : GI);
     hipStream_t st = ss::as_stream(stream);
     switch (n_est) {
     case 1:

@@ -1,46 +1,25 @@
 // The training objective (main_us3d.py:199-208, models/loss.py): the masked disparity loss, the label loss (cross-entropy with an ignored
 // class + multi-class Dice) and the left-right semantic consistency loss (the same cross-entropy with the label gathered along the row).
-// All three are streaming reductions: 256 threads, a capped grid with a grid-stride loop, 16-byte loads where the alignment allows.
-// Sums go thread (fp32, a few dozen terms) -> wave (double, shuffles) -> LDS -> one partial per workgroup in the caller's workspace ->
-// a one-workgroup launch that adds the partials in a fixed order in double and writes the record of sums and the scalar loss.  No
-// floating-point atomics: two calls on the same inputs return the same bits.  The backward launches recompute what they need from the
-// inputs and read only the record of sums and the incoming gradient from the device; nothing here allocates, copies or synchronises.
+// All three are streaming reductions in the form of stream.h: a thread's sums are fp32 (a few dozen terms), doubles from the wave on,
+// and the finish is a one-workgroup launch that writes the record of sums and the scalar loss.  The backward launches recompute what
+// they need from the inputs and read only the record of sums and the incoming gradient from the device; nothing here allocates, copies
+// or synchronises.
 #include "common.h"
+#include "metrics_decode.h"
+#include "stream.h"
 
 namespace {
 
-constexpr int NC = 6;         // classes (the reference's US3D setting, main_us3d.py: nums = 6)
-constexpr int BLOCK = 256;
+using namespace ss::stream;    // BLOCK, grid_for, aligned_to, aligned16, block_sum
+using ss::metrics::NC;         // (label_class is this file's own below, so no using-directive for ss::metrics)
+using ss::metrics::LT_I64;
+using ss::metrics::LT_U8;
+using ss::metrics::LT_F32;
+
 constexpr int GD = 512;       // workgroups per term of the disparity loss (x up to 4 terms)
 constexpr int GL = 2048;      // workgroups of the label loss
 constexpr int TERMS = 4;
 constexpr double DICE_EPS = 1e-6;     // models/loss.py:33
-
-__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// v[k] summed over the workgroup; the totals are valid in thread 0.  Fixed order: the shuffle tree, then waves 0..3.
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double* lds) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) lds[wave * K + k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) v[k] = (lds[k] + lds[K + k]) + (lds[2 * K + k] + lds[3 * K + k]);
-    }
-}
 
 // ---------------------------------------------------------------- disparity loss (models/loss.py:19-31)
 struct DispTerm {
@@ -76,7 +55,7 @@ __global__ __launch_bounds__(BLOCK) void disp_loss_fwd_k(DispArgs a) {
     __shared__ double lds[4 * 2];
     const DispTerm t = a.t[blockIdx.y];
     const long long stride = (long long)gridDim.x * BLOCK, first = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    const bool vec = aligned16(t.est) && aligned16(t.gt) && (!t.mask || (reinterpret_cast<uintptr_t>(t.mask) & 3) == 0);
+    const bool vec = aligned16(t.est) && aligned16(t.gt) && aligned_to(t.mask, 4);
     const long long n4 = vec ? t.n / 4 : 0;
     float s = 0.f;
     int c = 0;
@@ -128,7 +107,7 @@ __global__ __launch_bounds__(BLOCK) void disp_loss_bwd_k(DispArgs a) {
     if (!t.grad) return;
     const float k = (float)((double)a.gout[0] * (double)t.w / a.rec[2 * blockIdx.y + 1]);
     const long long stride = (long long)gridDim.x * BLOCK, first = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    const bool vec = aligned16(t.est) && aligned16(t.gt) && aligned16(t.grad) && (!t.mask || (reinterpret_cast<uintptr_t>(t.mask) & 3) == 0);
+    const bool vec = aligned16(t.est) && aligned16(t.gt) && aligned16(t.grad) && aligned_to(t.mask, 4);
     const long long n4 = vec ? t.n / 4 : 0;
     for (long long i = first; i < n4; i += stride) {
         const float4 e = reinterpret_cast<const float4*>(t.est)[i], g = reinterpret_cast<const float4*>(t.gt)[i];
@@ -148,8 +127,6 @@ __global__ __launch_bounds__(BLOCK) void disp_loss_bwd_k(DispArgs a) {
 }
 
 // ---------------------------------------------------------------- label loss and LRSC loss (models/loss.py:106-135)
-enum { LT_I64 = 0, LT_U8 = 1, LT_F32 = 2 };
-
 struct LabelArgs {
     const float* z;            // logits [B,NC,H,W]
     const void* y;             // labels [B,H,W], dtype by the kernel's template argument
@@ -172,7 +149,7 @@ __device__ __forceinline__ long long label_raw(const void* y, long long i) {
     const float f = reinterpret_cast<const float*>(y)[i];
     return (f > -9.0e18f && f < 9.0e18f) ? (long long)f : -1;       // .long() truncates; NaN and the out-of-range values are nobody's class
 }
-// a class in [0, NC), or -1: never an index out of bounds
+// a class in [0, NC), or -1: never an index out of bounds.  (Not metrics_decode.h's label_class on purpose: the raw value goes to `warped`.)
 __device__ __forceinline__ int label_class(long long v) { return (v < 0 || v >= NC) ? -1 : (int)v; }
 
 // the label of pixel p = (b, r) with r = h * W + x: its own, or (LRSC, models/loss.py:129-131) the one at xs = (long) clamp((float) x -
@@ -383,11 +360,6 @@ __global__ __launch_bounds__(BLOCK) void label_loss_bwd_k(LabelArgs a) {
 #pragma unroll
         for (int k = 0; k < NC; ++k) a.gz[off + k * HW] = g[k];
     }
-}
-
-int grid_for(long long work, int cap) {
-    const long long g = ss::ceil_div_ll(work, BLOCK);
-    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
 }
 
 template <int LT>

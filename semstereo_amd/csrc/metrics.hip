@@ -1,18 +1,16 @@
 // The evaluation step's metrics (main_us3d.py:225-263; utils/metrics.py): EPE / D1 / Thres of up to four estimates against one ground
 // truth in one pass, and the joint histogram of (label, argmax of the logits) behind the confusion matrix.  Both are streaming
-// reductions in the style of loss.hip: 256 threads, a capped grid with a grid-stride loop, 16-byte loads where the alignment allows,
-// four pixels per thread and trip.  Counts are integers from the thread up; the error sum is fp32 per thread (a few dozen terms) and a
-// double from the wave reduction on.  Each workgroup leaves one partial in the caller's workspace and a second small launch adds the
-// partials in a fixed order: no floating-point atomics, two calls on the same inputs return the same bits.  Nothing here allocates,
-// copies or synchronises, and nothing comes back to the host.
+// reductions in the form of stream.h.  Counts are integers from the thread up; the error sum is fp32 per thread (a few dozen terms) and
+// a double from the wave reduction on.  Nothing here allocates, copies or synchronises, and nothing comes back to the host.
 #include "common.h"
 #include "metrics_decode.h"
+#include "stream.h"
 
 namespace {
 
-using namespace ss::metrics;   // NC, NBIN, LT_*, label_row, argmax6, aligned16, wave_sum: shared with joint_metrics.hip
+using namespace ss::metrics;   // NC, NBIN, LT_*, label_row, argmax6
+using namespace ss::stream;    // BLOCK, grid_for, aligned_to, aligned16, wave_sum, block_sum
 
-constexpr int BLOCK = 256;
 constexpr int GM = 1024;       // workgroups of the disparity metrics, all images together
 constexpr int GC = 1024;       // workgroups of the confusion matrix
 constexpr int NEST = 4, NTHR = 4;
@@ -72,7 +70,7 @@ __global__ __launch_bounds__(BLOCK) void disp_metrics_k(MetricArgs a) {
     const unsigned char* mask = a.mask ? a.mask + base : nullptr;
     const unsigned char* mimg = a.mask_img ? a.mask_img + base : nullptr;
     const float* est[NE];
-    bool vec = aligned16(gt) && (!mask || (reinterpret_cast<uintptr_t>(mask) & 3) == 0) && (!mimg || (reinterpret_cast<uintptr_t>(mimg) & 3) == 0);
+    bool vec = aligned16(gt) && aligned_to(mask, 4) && aligned_to(mimg, 4);        // (a null mask passes)
 #pragma unroll
     for (int k = 0; k < NE; ++k) {
         est[k] = a.est[k] + base;
@@ -109,7 +107,7 @@ __global__ __launch_bounds__(BLOCK) void disp_metrics_k(MetricArgs a) {
         for (int k = 0; k < NE; ++k) e[k] = est[k][i];
         metric_point<NE>(a, gt[i], e, mask ? mask[i] : 0, mimg ? mimg[i] : 0, acc);
     }
-    // thread -> wave (shuffles) -> LDS -> thread 0, in a fixed order; the counts stay integers
+    // the counts stay integers
     int ci[NI];
     double cd[NE];
     ci[0] = acc.sel;
@@ -122,28 +120,16 @@ __global__ __launch_bounds__(BLOCK) void disp_metrics_k(MetricArgs a) {
 #pragma unroll
         for (int t = 0; t < NTHR; ++t) ci[4 + 5 * k + t] = acc.t[k][t];
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NI; ++k) ci[k] = wave_sum(ci[k]);
-#pragma unroll
-    for (int k = 0; k < NE; ++k) cd[k] = wave_sum(cd[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < NI; ++k) lds_i[wave * NI + k] = ci[k];
-#pragma unroll
-        for (int k = 0; k < NE; ++k) lds_d[wave * NE + k] = cd[k];
-    }
-    __syncthreads();
+    block_sum<NE>(cd, lds_d);
+    block_sum<NI>(ci, lds_i);
     if (threadIdx.x == 0) {
         double* p = a.ws + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * (3 + 6 * NE);
-#pragma unroll
-        for (int k = 0; k < NI; ++k) ci[k] = (lds_i[k] + lds_i[NI + k]) + (lds_i[2 * NI + k] + lds_i[3 * NI + k]);
         p[0] = (double)ci[0];
         p[1] = (double)ci[1];
         p[2] = (double)ci[2];
 #pragma unroll
         for (int k = 0; k < NE; ++k) {
-            p[3 + 6 * k] = (lds_d[k] + lds_d[NE + k]) + (lds_d[2 * NE + k] + lds_d[3 * NE + k]);
+            p[3 + 6 * k] = cd[k];
 #pragma unroll
             for (int t = 0; t < 5; ++t) p[4 + 6 * k + t] = (double)ci[3 + 5 * k + t];
         }
@@ -263,22 +249,11 @@ __global__ __launch_bounds__(BLOCK) void seg_confusion_k(ConfArgs a) {
 // the same bits)
 __global__ __launch_bounds__(BLOCK) void seg_confusion_finish_k(ConfArgs a, int G) {
     __shared__ long long lds[4];
-    const int k = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long v = 0;
-    for (int g = threadIdx.x; g < G; g += BLOCK) v += a.ws[(long long)g * NBIN + k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if (lane == 0) lds[wave] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const long long tot = (lds[0] + lds[1]) + (lds[2] + lds[3]);
-        a.out[k] = a.accumulate ? a.out[k] + tot : tot;
-    }
-}
-
-int grid_for(long long work, int cap) {
-    const long long g = ss::ceil_div_ll(work, BLOCK);
-    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
+    const int k = blockIdx.x;
+    long long v[1] = {0};
+    for (int g = threadIdx.x; g < G; g += BLOCK) v[0] += a.ws[(long long)g * NBIN + k];
+    block_sum<1>(v, lds);
+    if (threadIdx.x == 0) a.out[k] = a.accumulate ? a.out[k] + v[0] : v[0];
 }
 
 template <int NE>

@@ -1,5 +1,6 @@
-// What the evaluation kernels share (metrics.hip, joint_metrics.hip): the class of a label, the prediction of six logits, the
-// reductions of a wave.  One definition, so the joint record and the confusion matrix can never decode a pixel differently.
+// How a pixel is decoded, for every kernel that reads a label map or takes the prediction of the logits (metrics.hip,
+// joint_metrics.hip, vis.hip; loss.hip and sample_prep.hip share the dtype codes): the class of a label, np.argmax's rule.  One
+// definition, so the joint record, the confusion matrix and the colours of one pixel can never differ.
 #pragma once
 #include "common.h"
 
@@ -11,21 +12,8 @@ constexpr int NBIN = (NC + 1) * NC;      // joint histogram: label 0..5 and "out
 
 enum { LT_I64 = 0, LT_U8 = 1, LT_F32 = 2 };      // include/semstereo_hip.h: label_dtype
 
-__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // the class of a label in [0, NC), or NC for "outside": never an index out of bounds.  Float labels truncate toward zero as the
-// reference's np.asarray(..., dtype=int) does; NaN is outside.
+// reference's np.asarray(..., dtype=int) and label.to(torch.int64) do; NaN is outside.
 __device__ __forceinline__ int label_class(long long v) { return (v < 0 || v >= NC) ? NC : (int)v; }
 __device__ __forceinline__ int label_class(unsigned char v) { return v >= NC ? NC : (int)v; }
 __device__ __forceinline__ int label_class(float f) { return (f > -1.f && f < (float)NC) ? (int)f : NC; }
@@ -37,13 +25,16 @@ __device__ __forceinline__ int label_row(const void* y, long long i) {
     return label_class(reinterpret_cast<const float*>(y)[i]);
 }
 
-// np.argmax: the lowest index among equal maxima, and a NaN counts as the maximum (the first one wins)
+// np.argmax: the lowest index among equal maxima, and a NaN counts as the maximum (the first one wins).  Whether a later channel's z
+// replaces the best so far (three compares and no branch: & and | on purpose):
+__device__ __forceinline__ bool argmax_take(float best, float z) { return (best == best) & ((z > best) | (z != z)); }
+
 __device__ __forceinline__ int argmax6(const float (&z)[NC]) {
     float best = z[0];
     int idx = 0;
 #pragma unroll
     for (int k = 1; k < NC; ++k) {
-        const bool take = best == best && (z[k] > best || z[k] != z[k]);
+        const bool take = argmax_take(best, z[k]);
         best = take ? z[k] : best;
         idx = take ? k : idx;
     }

@@ -6,15 +6,20 @@
 //              disparity_4/8/16, label_2/4 and the float32 label (and disparity, for an integer source) in one launch
 //   luma       PIL's convert("L"), (19595 R + 38470 G + 7471 B + 0x8000) >> 16, with the per-image integer sums S1 and S2
 //   gradients  z = (L - mean) / std in double from the exact sums, gx = z(y, x-1) - z(y, x+1), gy = z(y-1, x) - z(y+1, x), zero outside
-// All of them are streaming passes of 256 threads, a capped grid with a grid-stride loop, a lane taking 4 consecutive pixels of one row
-// (one wide access where the address allows, scalars otherwise and at a ragged end).  Element offsets are 64-bit.  No atomics: the luma
-// pass leaves one pair of 64-bit integer partial sums per workgroup, which the gradient pass adds; integer sums are exact in any order.
-// Nothing here allocates, copies or synchronises, and nothing comes back to the host.
+// All of them are streaming passes of the stream.h family, a lane taking a row quad (4 consecutive pixels of one row).  Element offsets
+// are 64-bit.  The luma pass leaves one pair of 64-bit integer partial sums per workgroup, which the gradient pass adds; integer sums
+// are exact in any order.  Nothing here allocates, copies or synchronises, and nothing comes back to the host.
 #include "common.h"
+#include "metrics_decode.h"
+#include "stream.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
+using namespace ss::stream;    // BLOCK, grid_for, aligned_to, block_sum, RowQuad, row_quad, store4
+using ss::metrics::LT_I64;     // label sources: the codes of every label_dtype
+using ss::metrics::LT_U8;
+using ss::metrics::LT_F32;
+
 constexpr int GV = 2048;                 // workgroups of a pass, all images together
 constexpr long long MAX_STAT_PIXELS = 1ll << 23;      // N S2 - S1^2 is formed in 64 unsigned bits: N <= 2^23 keeps N S2 below 2^62
 constexpr long long SUMS_ALIGN = 256;    // the luma plane starts at a multiple of this behind the partial sums
@@ -22,30 +27,6 @@ constexpr int MAX_STAT_GROUPS = 1024;    // workgroups (and partial sums) per im
 
 typedef unsigned long long u64;
 typedef unsigned char u8;
-
-__device__ __forceinline__ bool aligned_to(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(a - 1)) == 0; }
-
-__device__ __forceinline__ void store4(float* p, int nv, const float (&v)[4]) {
-    if (nv == 4 && aligned_to(p, 16)) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < nv) p[j] = v[j];
-    }
-}
-
-// The 4-pixel groups of all rows of a [B,H,W] map, numbered row by row (QW = ceil(W / 4) per row); the launchers keep their number below
-// 2^31, so row and column come from 32-bit divisions.
-struct RowQuad {
-    unsigned b, h;
-    int x0, nv;
-};
-__device__ __forceinline__ RowQuad row_quad(unsigned q, unsigned QW, unsigned H, int W) {
-    const unsigned row = q / QW, qx = q - row * QW, b = row / H;
-    const int x0 = (int)(qx * 4u), left = W - x0;
-    return RowQuad{b, row - b * H, x0, left < 4 ? left : 4};
-}
 
 // 4 interleaved RGB pixels (12 bytes) at p as three little-endian words: three dword loads, or 3 nv byte loads (the rest zero)
 __device__ __forceinline__ void load_rgb4(const u8* p, int nv, unsigned (&w)[3]) {
@@ -98,7 +79,6 @@ __global__ __launch_bounds__(BLOCK) void views_k(ViewArgs a) {
 
 // ---------------------------------------------------------------- pyramids (cv2.resize INTER_NEAREST, H and W divisible by k)
 enum { DT_F32 = 0, DT_I32 = 1 };                 // disparity sources
-enum { LT_I64 = 0, LT_U8 = 1, LT_F32 = 2 };      // label sources: the codes of ss_class_color_fwd
 constexpr int NJOBS = 7;                         // disparity, disparity_4/8/16, label, label_2/4
 
 struct PyrArgs {
@@ -188,32 +168,14 @@ __global__ __launch_bounds__(BLOCK) void pyramid_k(PyrArgs a) {
 // ---------------------------------------------------------------- luma and the per-image sums
 __device__ __forceinline__ unsigned luma_of(unsigned r, unsigned g, unsigned b) { return (19595u * r + 38470u * g + 7471u * b + 0x8000u) >> 16; }
 
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// thread -> wave (shuffles) -> LDS -> every thread: the workgroup's sums of a and b
-__device__ __forceinline__ void block_sum2(u64& a, u64& b, u64 (&lds)[2][BLOCK / 64]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    a = wave_sum(a);
-    b = wave_sum(b);
-    if (lane == 0) lds[0][wave] = a, lds[1][wave] = b;
-    __syncthreads();
-    a = b = 0ull;
-#pragma unroll
-    for (int k = 0; k < BLOCK / 64; ++k) a += lds[0][k], b += lds[1][k];
-}
-
 // grid (G, B): image blockIdx.y of n pixels, 4 consecutive ones per lane and trip; the workgroup's partial S1, S2 go to
 // sums[(b * G + g) * 2 + {0, 1}]
 __global__ __launch_bounds__(BLOCK) void luma_stats_k(const u8* src, long long n, u8* luma, u64* sums) {
-    __shared__ u64 lds[2][BLOCK / 64];
+    __shared__ u64 lds[4 * 2];
     const u8* p = src + (long long)blockIdx.y * n * 3;
     u8* o = luma + (long long)blockIdx.y * n;
     const long long nq = (n + 3) / 4, stride = (long long)gridDim.x * BLOCK;
-    u64 s1 = 0ull, s2 = 0ull;
+    u64 s[2] = {0ull, 0ull};           // S1, S2
     for (long long q = (long long)blockIdx.x * BLOCK + threadIdx.x; q < nq; q += stride) {
         const long long left = n - 4 * q;
         const int nv = left < 4 ? (int)left : 4;
@@ -227,8 +189,8 @@ __global__ __launch_bounds__(BLOCK) void luma_stats_k(const u8* src, long long n
             t1 += L[j];
             t2 += L[j] * L[j];
         }
-        s1 += t1;
-        s2 += t2;
+        s[0] += t1;
+        s[1] += t2;
         u8* d = o + 4 * q;
         if (nv == 4 && aligned_to(d, 4)) {
             *reinterpret_cast<unsigned*>(d) = packed;
@@ -238,10 +200,10 @@ __global__ __launch_bounds__(BLOCK) void luma_stats_k(const u8* src, long long n
                 if (j < nv) d[j] = (u8)L[j];
         }
     }
-    block_sum2(s1, s2, lds);
+    block_sum<2>(s, lds);
     if (threadIdx.x == 0) {
         u64* w = sums + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 2;
-        w[0] = s1, w[1] = s2;
+        w[0] = s[0], w[1] = s[1];
     }
 }
 
@@ -270,15 +232,16 @@ __device__ __forceinline__ void row_window(const u8* row, int x0, int nv, int W,
 // luma value; the centre tap of the reference's convolution, 0 z(y, x), is kept so that such a pixel is NaN whatever its neighbours are.
 __global__ __launch_bounds__(BLOCK) void gradients_k(const u8* luma, const u64* sums, int GS, float* gx, float* gy, int H, int W) {
     __shared__ double z[256];
-    __shared__ u64 lds[2][BLOCK / 64];
+    __shared__ u64 lds[4 * 2];
     const u64 N = (u64)H * (u64)W;
-    u64 S1 = 0ull, S2 = 0ull;
+    u64 s[2] = {0ull, 0ull};
     for (int g = threadIdx.x; g < GS; g += BLOCK) {
         const u64* w = sums + ((long long)blockIdx.y * GS + g) * 2;
-        S1 += w[0], S2 += w[1];
+        s[0] += w[0], s[1] += w[1];
     }
-    block_sum2(S1, S2, lds);
+    block_sum<2>(s, lds);              // (the totals in every thread)
     {
+        const u64 S1 = s[0], S2 = s[1];
         const double n = (double)N, mean = (double)S1 / n, sd = sqrt((double)(N * S2 - S1 * S1)) / n;
         z[threadIdx.x] = ((double)(int)threadIdx.x - mean) / sd;
     }
@@ -309,11 +272,6 @@ __global__ __launch_bounds__(BLOCK) void gradients_k(const u8* luma, const u64* 
         store4(ox + (long long)h * W + x0, nv, vx);
         store4(oy + (long long)h * W + x0, nv, vy);
     }
-}
-
-int grid_for(long long work, int cap) {
-    const long long g = ss::ceil_div_ll(work, BLOCK);
-    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
 }
 
 // 4-pixel groups of a [B,H,W] map, or -1 where the map has 2^31 elements or more

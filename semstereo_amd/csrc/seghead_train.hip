@@ -22,6 +22,7 @@
 // bias: wave shuffles -> LDS), one partial per workgroup in `workspace`, and a second small launch adds the partials in double in a
 // fixed order.  No floating-point atomics: two calls give the same bits.
 #include "common.h"
+#include "stream.h"
 
 namespace {
 
@@ -322,7 +323,7 @@ int tail_check(int B, int K, int C, int H, int W, int up2, long long* tiles) {
     return SS_OK;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using ss::stream::aligned16;
 
 }  // namespace
 

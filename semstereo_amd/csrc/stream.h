@@ -1,0 +1,136 @@
+// What the streaming kernels share (loss.hip, metrics.hip, joint_metrics.hip, vis.hip, sample_prep.hip).  They are all one kind of
+// kernel: BLOCK threads, a capped grid with a grid-stride loop, a lane takes 4 consecutive elements (one wide access where the address
+// allows, scalars otherwise), and a reduction goes thread -> wave (shuffles) -> LDS -> one partial per workgroup in the caller's
+// workspace -> a small finish launch that adds the partials in a fixed order.  No floating-point atomics anywhere: two calls on the
+// same inputs return the same bits.  The order of that sum is written down here, once.
+#pragma once
+#include "common.h"
+
+namespace ss {
+namespace stream {
+
+constexpr int BLOCK = 256;     // threads of every streaming kernel: four waves
+
+// workgroups for `work` lane-trips: one trip per lane where that fits under `cap`, never fewer than one
+inline int grid_for(long long work, int cap) {
+    const long long g = ceil_div_ll(work, BLOCK);
+    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
+}
+
+// a: a power of two.  A null pointer is aligned, so an optional tensor needs no test of its own.
+__host__ __device__ __forceinline__ bool aligned_to(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(a - 1)) == 0; }
+__host__ __device__ __forceinline__ bool aligned16(const void* p) { return aligned_to(p, 16); }
+
+// ---------------------------------------------------------------- reductions
+// The shuffle-down tree 32, 16, ..., 1: the total is valid in lane 0.  T: double, int, long long, unsigned long long.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_down(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
+    return v;
+}
+
+// v[k] summed over the workgroup, every k; lds holds 4 * K elements.  The order is fixed and is part of the recorded bits: in a wave
+// the shuffle-down tree of wave_sum, then the four waves' totals as (w0 + w1) + (w2 + w3).
+//   - The totals land in EVERY thread (gradients_k builds its table from them in all 256; a kernel that writes a partial uses thread 0's).
+//   - The helper owns the leading barrier: no lane writes lds before every thread is done with what it held, so calls may follow each
+//     other on the same lds (disp_loss_finish_k calls it in a loop) and the caller adds no barrier of its own.
+template <int K, typename T>
+__device__ __forceinline__ void block_sum(T (&v)[K], T* lds) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) lds[wave * K + k] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = (lds[k] + lds[K + k]) + (lds[2 * K + k] + lds[3 * K + k]);
+}
+
+// the same for a minimum and a maximum (lds: 8 floats); both decisions above hold
+__device__ __forceinline__ void block_minmax(float& lo, float& hi, float* lds) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    lo = wave_min(lo);
+    hi = wave_max(hi);
+    __syncthreads();
+    if (lane == 0) lds[wave] = lo, lds[4 + wave] = hi;
+    __syncthreads();
+    lo = fminf(fminf(lds[0], lds[1]), fminf(lds[2], lds[3]));
+    hi = fmaxf(fmaxf(lds[4], lds[5]), fmaxf(lds[6], lds[7]));
+}
+
+// ---------------------------------------------------------------- 4 consecutive elements of a row
+// The 4-pixel groups of all rows of a [B,H,W] map are numbered row by row (QW = ceil(W / 4) per row); the launchers keep their number
+// below 2^31, so the group's row and column come from 32-bit divisions and only the element offsets are 64-bit.
+struct RowQuad {
+    unsigned b, h;
+    int x0, nv;                // first column, and how many of the 4 lie inside the row
+};
+__device__ __forceinline__ RowQuad row_quad(unsigned q, unsigned QW, unsigned H, int W) {
+    const unsigned row = q / QW, qx = q - row * QW, b = row / H;
+    const int x0 = (int)(qx * 4u), left = W - x0;
+    return RowQuad{b, row - b * H, x0, left < 4 ? left : 4};
+}
+
+// one wide access, or nv scalars (a load leaves the rest zero)
+__device__ __forceinline__ void load4(const float* p, int nv, float (&v)[4]) {
+    if (nv == 4 && aligned_to(p, 16)) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[j] : 0.f;
+    }
+}
+__device__ __forceinline__ void load4(const unsigned char* p, int nv, unsigned char (&v)[4]) {
+    if (nv == 4 && aligned_to(p, 4)) {
+        const uchar4 q = *reinterpret_cast<const uchar4*>(p);
+        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[j] : (unsigned char)0;
+    }
+}
+__device__ __forceinline__ void load4(const long long* p, int nv, long long (&v)[4]) {
+    if (nv == 4 && aligned_to(p, 16)) {
+        const longlong2 a = reinterpret_cast<const longlong2*>(p)[0], b = reinterpret_cast<const longlong2*>(p)[1];
+        v[0] = a.x, v[1] = a.y, v[2] = b.x, v[3] = b.y;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[j] : 0ll;
+    }
+}
+__device__ __forceinline__ void store4(float* p, int nv, const float (&v)[4]) {
+    if (nv == 4 && aligned_to(p, 16)) {
+        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < nv) p[j] = v[j];
+    }
+}
+__device__ __forceinline__ void store4(unsigned char* p, int nv, const float (&v)[4]) {
+    if (nv == 4 && aligned_to(p, 4)) {
+        *reinterpret_cast<uchar4*>(p) = make_uchar4((unsigned char)v[0], (unsigned char)v[1], (unsigned char)v[2], (unsigned char)v[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < nv) p[j] = (unsigned char)v[j];
+    }
+}
+
+}  // namespace stream
+}  // namespace ss

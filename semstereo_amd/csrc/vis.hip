@@ -1,81 +1,22 @@
 // The evaluation step's image outputs (main_us3d.py:252, :265-268; main_whu.py:242, :250-251): the D1-style error map of
 // utils/visualization.py:30-55, the class colours of utils/mask_vis.py:5-31 and the per-image min/max normalisation that
-// utils/experiment.py:84-99 asks of make_grid.  All of them are streaming passes without atomics: 256 threads, a capped grid with a
-// grid-stride loop, a lane takes 4 consecutive pixels of one row -- one 16-byte access where the address allows, scalars otherwise and
-// at the end of a row whose width is no multiple of 4 -- and writes the planar [B,3,H,W] result.  Element offsets are 64-bit.  Every
-// division is the IEEE one (no reciprocal, no fast-math): the error map is compared with the reference's bit for bit.
-// Nothing here allocates, copies or synchronises, and nothing comes back to the host.
+// utils/experiment.py:84-99 asks of make_grid.  All of them are streaming passes of the stream.h family: a lane takes a row quad (4
+// consecutive pixels of one row) and writes the planar [B,3,H,W] result; labels and logits are decoded by metrics_decode.h, as the
+// confusion matrix decodes them.  Element offsets are 64-bit.  Every division is the IEEE one (no reciprocal, no fast-math): the error
+// map is compared with the reference's bit for bit.  Nothing here allocates, copies or synchronises, and nothing comes back to the host.
 #include "common.h"
+#include "metrics_decode.h"
+#include "stream.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
+using namespace ss::metrics;   // NC (the palette of utils/mask_vis.py:10-15 has as many colours), LT_*, label_class, argmax_take
+using namespace ss::stream;    // BLOCK, grid_for, aligned_to, block_minmax, RowQuad, row_quad, load4, store4
+
 constexpr int GV = 2048;       // workgroups of the per-pixel passes
 constexpr int GR = 1024;       // workgroups of the min/max reduction, all images together
 constexpr int NBINS = 10;      // rows of the error colour table (utils/visualization.py:11-24)
-constexpr int NCOL = 6;        // classes of the palette (utils/mask_vis.py:10-15)
 constexpr int LEGEND_ROWS = 10, LEGEND_STEP = 20;          // utils/visualization.py:51-53
-
-__device__ __forceinline__ bool aligned_to(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(a - 1)) == 0; }
-
-// ---------------------------------------------------------------- 4 consecutive elements of a row: one wide access or nv scalars
-__device__ __forceinline__ void load4(const float* p, int nv, float (&v)[4]) {
-    if (nv == 4 && aligned_to(p, 16)) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[j] : 0.f;
-    }
-}
-__device__ __forceinline__ void load4(const unsigned char* p, int nv, unsigned char (&v)[4]) {
-    if (nv == 4 && aligned_to(p, 4)) {
-        const uchar4 q = *reinterpret_cast<const uchar4*>(p);
-        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[j] : (unsigned char)0;
-    }
-}
-__device__ __forceinline__ void load4(const long long* p, int nv, long long (&v)[4]) {
-    if (nv == 4 && aligned_to(p, 16)) {
-        const longlong2 a = reinterpret_cast<const longlong2*>(p)[0], b = reinterpret_cast<const longlong2*>(p)[1];
-        v[0] = a.x, v[1] = a.y, v[2] = b.x, v[3] = b.y;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[j] : 0ll;
-    }
-}
-__device__ __forceinline__ void store4(float* p, int nv, const float (&v)[4]) {
-    if (nv == 4 && aligned_to(p, 16)) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < nv) p[j] = v[j];
-    }
-}
-__device__ __forceinline__ void store4(unsigned char* p, int nv, const float (&v)[4]) {
-    if (nv == 4 && aligned_to(p, 4)) {
-        *reinterpret_cast<uchar4*>(p) = make_uchar4((unsigned char)v[0], (unsigned char)v[1], (unsigned char)v[2], (unsigned char)v[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < nv) p[j] = (unsigned char)v[j];
-    }
-}
-
-// The 4-pixel groups of all rows are numbered row by row (QW = ceil(W / 4) per row); the launchers keep their number below 2^31, so
-// the group's row and column come from 32-bit divisions and only the element offsets are 64-bit.
-struct RowQuad {
-    unsigned b, h;
-    int x0, nv;
-};
-__device__ __forceinline__ RowQuad row_quad(unsigned q, unsigned QW, unsigned H, int W) {
-    const unsigned row = q / QW, qx = q - row * QW, b = row / H;
-    const int x0 = (int)(qx * 4u), left = W - x0;
-    return RowQuad{b, row - b * H, x0, left < 4 ? left : 4};
-}
 
 // ---------------------------------------------------------------- error map (utils/visualization.py:30-55)
 struct ErrArgs {
@@ -136,7 +77,7 @@ __global__ __launch_bounds__(BLOCK) void error_image_k(ErrArgs a) {
 }
 
 // ---------------------------------------------------------------- class colours (utils/mask_vis.py:5-31)
-enum { SRC_LOGITS = -1, LT_I64 = 0, LT_U8 = 1, LT_F32 = 2 };
+constexpr int SRC_LOGITS = -1;         // src_dtype: the logits, or one of LT_*
 
 struct ColorArgs {
     const void* src;           // logits [B,C,H,W] fp32, or labels: pixel (b, h, x) at b * y_img + h * y_row + x
@@ -144,12 +85,6 @@ struct ColorArgs {
     long long y_row, y_img;
     int B, C, H, W;
 };
-
-// the class of a label in [0, 6), or 6 for "outside" (black).  Float labels truncate toward zero as label.to(torch.int64) does
-// (main_us3d.py:266); NaN is outside.
-__device__ __forceinline__ int label_class(long long v) { return (v < 0 || v >= NCOL) ? NCOL : (int)v; }
-__device__ __forceinline__ int label_class(unsigned char v) { return v >= NCOL ? NCOL : (int)v; }
-__device__ __forceinline__ int label_class(float f) { return (f > -1.f && f < (float)NCOL) ? (int)f : NCOL; }
 
 // the palette of utils/mask_vis.py:10-15 as three bit sets over the class: black, red, green, blue, yellow, cyan; class 6 = black
 __device__ __forceinline__ void palette(int cls, float& r, float& g, float& b) {
@@ -175,20 +110,20 @@ __global__ __launch_bounds__(BLOCK) void class_color_k(ColorArgs a) {
         const RowQuad r = row_quad(q, QW, (unsigned)a.H, a.W);
         int cls[4];
         if (SRC == SRC_LOGITS) {
-            // np.argmax over the channels: the lowest index among equal maxima, a NaN counts as the maximum (the first one wins)
+            // argmax6's rule over the a.C <= NC channels, four pixels at a time
             const float* z = reinterpret_cast<const float*>(a.src) + ((long long)r.b * a.C * a.H + r.h) * a.W + r.x0;
             float best[4];
             load4(z, r.nv, best);
 #pragma unroll
             for (int j = 0; j < 4; ++j) cls[j] = 0;
 #pragma unroll
-            for (int k = 1; k < NCOL; ++k) {
+            for (int k = 1; k < NC; ++k) {
                 if (k < a.C) {
                     float zk[4];
                     load4(z + k * HW, r.nv, zk);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const bool take = best[j] == best[j] && (zk[j] > best[j] || zk[j] != zk[j]);
+                        const bool take = argmax_take(best[j], zk[j]);
                         best[j] = take ? zk[j] : best[j];
                         cls[j] = take ? k : cls[j];
                     }
@@ -214,31 +149,9 @@ __global__ __launch_bounds__(BLOCK) void class_color_k(ColorArgs a) {
 }
 
 // ---------------------------------------------------------------- per-image min / max and the normalisation (utils/experiment.py:98)
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_down(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
-    return v;
-}
-
-// thread -> wave (shuffles) -> LDS -> thread 0, in a fixed order; the result is valid in thread 0
-__device__ __forceinline__ void block_minmax(float& lo, float& hi, float (&lds)[2][4]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    lo = wave_min(lo);
-    hi = wave_max(hi);
-    if (lane == 0) lds[0][wave] = lo, lds[1][wave] = hi;
-    __syncthreads();
-    lo = fminf(fminf(lds[0][0], lds[0][1]), fminf(lds[0][2], lds[0][3]));
-    hi = fmaxf(fmaxf(lds[1][0], lds[1][1]), fmaxf(lds[1][2], lds[1][3]));
-}
-
 // grid (G, B): image blockIdx.y of n elements; the workgroup's partial goes to ws[(b * G + g) * 2 + {0, 1}]
 __global__ __launch_bounds__(BLOCK) void image_minmax_k(const float* x, long long n, float* ws) {
-    __shared__ float lds[2][4];
+    __shared__ float lds[8];
     const float* p = x + (long long)blockIdx.y * n;
     const long long stride = (long long)gridDim.x * BLOCK, first = (long long)blockIdx.x * BLOCK + threadIdx.x;
     const long long n4 = aligned_to(p, 16) ? n / 4 : 0;
@@ -262,7 +175,7 @@ __global__ __launch_bounds__(BLOCK) void image_minmax_k(const float* x, long lon
 
 // grid B: workgroup b folds the G partials of image b (thread t takes g = t, t + 256, ...) and writes minmax[b] = {min, max}
 __global__ __launch_bounds__(BLOCK) void image_minmax_finish_k(const float* ws, int G, float* minmax) {
-    __shared__ float lds[2][4];
+    __shared__ float lds[8];
     const float inf = __builtin_huge_valf();
     float lo = inf, hi = -inf;
     for (int g = threadIdx.x; g < G; g += BLOCK) {
@@ -299,11 +212,6 @@ __global__ __launch_bounds__(BLOCK) void image_normalize_k(const float* x, const
         const float w = (fminf(fmaxf(p[i], lo), hi) - lo) / den;
         for (int k = 0; k < rep; ++k) o[k * HW + i] = w;
     }
-}
-
-int grid_for(long long work, int cap) {
-    const long long g = ss::ceil_div_ll(work, BLOCK);
-    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
 }
 
 // 4-pixel groups of a [B,H,W] map, or -1 where they do not fit the kernels' 32-bit numbering
@@ -350,7 +258,7 @@ extern "C" int ss_class_color_fwd(const void* src, int src_dtype, int B, int num
     SS_REQUIRE(src_dtype >= SRC_LOGITS && src_dtype <= LT_F32 && (out_dtype == 0 || out_dtype == 1));
     if (src_dtype == SRC_LOGITS) {
         SS_REQUIRE(num_classes > 0);
-        if (num_classes > NCOL) return SS_ERR_UNSUPPORTED;
+        if (num_classes > NC) return SS_ERR_UNSUPPORTED;
     } else {
         SS_REQUIRE(label_row_stride >= W && label_image_stride >= (long long)(H - 1) * label_row_stride + W);
     }

@@ -17,9 +17,9 @@ import torch
 
 from . import _lib
 from . import engine as E
-from ._host import LABEL_CODES, _c, _nograd, count
+from ._host import LABEL_CODES, _c, _label_classes, _nograd, argmax_first, count
 from ._lib import call, ptr
-from .metrics import NCLS, _as_bool, _check_shapes, argmax_first, supported_confusion, supported_disparity
+from .metrics import NCLS, _as_bool, _check_shapes, supported_confusion, supported_disparity
 
 FLAG_FIELDS = ("n_d1", "n_thr0", "n_thr1", "n_thr2", "n_thr3")        # record["cls_counts"][..., i]
 RECORD_KEYS = ("image", "cls_sel", "cls_counts", "cls_sums", "joint_all", "joint_out", "joint_good")
@@ -28,18 +28,6 @@ RECORD_KEYS = ("image", "cls_sel", "cls_counts", "cls_sums", "joint_all", "joint
 def scratch_bytes(n_est, B):
     """Scratch of ss_joint_metrics_fwd."""
     return _lib.query_bytes("ss_joint_metrics_scratch", n_est, B)
-
-
-def _label_classes(labels, C, H, W):
-    """int64 [B,H,W]: the class of a label in [0, C), or C for "outside", labels cropped to H x W (metrics._joint_torch's decoding)."""
-    y = labels[:, :H, :W]
-    if y.is_floating_point():
-        inside = (y > -1) & (y < C)                                # truncation toward zero, NaN outside
-        y = torch.where(inside, y, torch.zeros_like(y)).long()
-    else:
-        y = y.long()
-        inside = (y >= 0) & (y < C)
-    return torch.where(inside, y, torch.full_like(y, C))
 
 
 def _bins(index, weight, n):
@@ -53,7 +41,7 @@ def _joint_torch(ests, logits, gt, labels, mask, rng, thresholds, tau, C):
     B, H, W = gt.shape
     dev = gt.device
     inmask = _as_bool(mask) if mask is not None else (gt >= rng[0]) & (gt < rng[1])
-    g = _label_classes(labels, C, H, W)
+    g = _label_classes(labels[:, :H, :W], C)
     img = torch.arange(B, device=dev).view(B, 1, 1)
     row = img * (C + 1) + g                                        # (image, class)
     rec = {"image": torch.stack([inmask.sum((1, 2)), (gt > 0).sum((1, 2))], dim=1),

@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from . import engine as E
-from ._host import LABEL_CODES, _c, _nograd, count
+from ._host import LABEL_CODES, _c, _label_classes, _nograd, argmax_first, count          # (argmax_first: also this module's name for it)
 from ._lib import call, ptr
 
 NCLS = 6                                   # channels the confusion kernel is built for
@@ -183,29 +183,10 @@ def Thres_metric_mask(D_ests, D_gts, masks, thres, mask_img):
 
 
 # ------------------------------------------------------------------------------------------------ confusion matrix
-def argmax_first(logits):
-    """np.argmax over the channel axis as elementwise selects: the lowest index among equal maxima, a NaN counts as the maximum."""
-    best = logits[:, 0]
-    idx = torch.zeros(best.shape, dtype=torch.int64, device=logits.device)
-    for k in range(1, logits.shape[1]):
-        z = logits[:, k]
-        take = ~torch.isnan(best) & ((z > best) | torch.isnan(z))
-        best = torch.where(take, z, best)
-        idx = torch.where(take, torch.full_like(idx, k), idx)
-    return idx
-
-
 def _joint_torch(logits, labels):
     """int64 [C + 1, C]: label class (row C: no class of the logits) x prediction, labels cropped to the logits' H, W."""
     B, C, H, W = logits.shape
-    y = labels[:, :H, :W]
-    if y.is_floating_point():
-        inside = (y > -1) & (y < C)                                # truncation toward zero, NaN outside
-        y = torch.where(inside, y, torch.zeros_like(y)).long()
-    else:
-        y = y.long()
-        inside = (y >= 0) & (y < C)
-    g = torch.where(inside, y, torch.full_like(y, C))
+    g = _label_classes(labels[:, :H, :W], C)
     index = (g * C + argmax_first(logits)).reshape(-1)
     joint = torch.zeros((C + 1) * C, dtype=torch.int64, device=logits.device)
     joint.index_add_(0, index, torch.ones_like(index))

@@ -29,9 +29,8 @@ import torch
 
 from . import _lib
 from . import engine as E
-from ._host import LABEL_CODES, _c, _const, _nograd, count
+from ._host import LABEL_CODES, _c, _const, _label_classes, _nograd, argmax_first, count
 from ._lib import call, ptr
-from .metrics import argmax_first
 
 NCLS = 6                                   # classes of the palette and channels the kernel takes
 NAMES = ("disp_error_image_func", "feature_vis")        # what install_visualization rebinds
@@ -151,14 +150,6 @@ def _colours_torch(cls, dtype):
     return _palette(cls.device, dtype)[cls].permute(0, 3, 1, 2).contiguous()
 
 
-def _label_classes(y):
-    if y.is_floating_point():
-        inside = (y > -1) & (y < NCLS)                             # truncation toward zero, NaN outside
-        return torch.where(inside, y, torch.full_like(y, NCLS)).long()
-    y = y.long()
-    return torch.where((y >= 0) & (y < NCLS), y, torch.full_like(y, NCLS))
-
-
 def _color_hip(src, code, B, C, H, W, row, img, dtype):
     out = torch.empty((B, 3, H, W), dtype=dtype, device=src.device)
     with torch.cuda.device(src.device):
@@ -194,7 +185,7 @@ def label_vis(labels, dtype=torch.float32):
         image_stride = max(y.stride(0), (H - 1) * y.stride(1) + W)                 # (the stride of a batch of one is arbitrary)
         return _color_hip(y, LABEL_CODES[y.dtype], B, NCLS, H, W, y.stride(1), image_stride, dtype)
     count("vis_torch")
-    return _colours_torch(_label_classes(labels), dtype)
+    return _colours_torch(_label_classes(labels, NCLS), dtype)
 
 
 # ------------------------------------------------------------------------------------------------ normalisation
