@@ -856,6 +856,32 @@ int ss_prep_luma_stats_fwd(const unsigned char* left, int B, int H, int W, void*
  * gx = float(z(y, x-1) - z(y, x+1)), gy = float(z(y-1, x) - z(y+1, x)), zero outside the image (convolve2d flips the kernel).  The
  * centre tap 0 * z(y, x) is kept: a constant image (std = 0) is NaN on every pixel, as in the reference. */
 int ss_prep_gradients_fwd(const void* workspace, long long workspace_bytes, int B, int H, int W, float* gx, float* gy, ss_stream_t stream);
+/* ---- right-view ground truth and the left-right consistency check, csrc/right_view.hip ----
+ * The forward warp the reference left as a commented-out per-pixel loop (datasets/us3d_.py:115-133, "label_r" at :193) and that
+ * LRSC_loss (models/loss.py:121-135) stands in for.  Row-wise, per image and row; d = disparity [B,H,W] float32 of the LEFT view, a left
+ * pixel x matching right column x - d (SpatialTransformer_grid's convention):
+ *   valid    lo <= d < hi; a NaN is not valid
+ *   target   t = rintf(float(x) - d) in fp32, half to even (np.round, torch.round); x LANDS if it is valid and 0 <= t < W.  -0.5 rounds
+ *            to -0 and lands in column 0; W - 0.5 rounds to W, outside the row, only for an even W
+ *   owner    of right column r: the LARGEST x that lands on r, -1 if none -- the last writer of a raster-order loop and, the pixel
+ *            further right having the larger disparity up to the rounding step, the surface nearer the sensor
+ *   right_disparity[r] = d[owner], else fill_disparity;  right_label[r] = float(label[owner]), else fill_label;
+ *   left_visible[x]    = lands(x) and owner[t(x)] == x, one byte 0 / 1
+ * No value is interpolated: every output is a selection, so the PyTorch composition gives the same bits.  One workgroup per row; the
+ * owners are an integer maximum in LDS (order-independent: two calls give the same bits), no floating-point atomics.  label: label_dtype
+ * 0 = int64, 1 = uint8, 2 = float32, pixel (b, h, x) at b * label_image_stride + h * label_row_stride + x elements.  Any output may be
+ * NULL and is then skipped, at least one is required; label is NULL exactly when right_label is.  lo >= hi or a NaN range: -1.
+ * W > 8192 (32 KB of owners), 2^31 or more elements, 2^31 or more rows: -2. */
+int ss_right_view_fwd(const float* disparity, const void* label, int label_dtype, long long label_row_stride,
+                      long long label_image_stride, int B, int H, int W, float lo, float hi, float fill_disparity, float fill_label,
+                      float* right_disparity, float* right_label, unsigned char* left_visible, ss_stream_t stream);
+/* Left-right consistency of two estimates in the convention above: disp_right[r] is the disparity of RIGHT pixel r (its left match at
+ * r + disp_right[r]) -- the form right_disparity has, and minus what the model returns for the swapped pair.
+ *   diff[x] = |disp_left[x] - disp_right[t(x)]| in fp32 where x lands and disp_right[t(x)] is valid, +inf elsewhere
+ *   consistent[x] = diff[x] <= threshold, one byte 0 / 1
+ * consistent or diff may be NULL, not both.  A negative or NaN threshold, lo >= hi or a NaN range: -1.  2^31 or more elements: -2. */
+int ss_lr_consistency_fwd(const float* disp_left, const float* disp_right, int B, int H, int W, float lo, float hi, float threshold,
+                          unsigned char* consistent, float* diff, ss_stream_t stream);
 /* Measurement aid (bench.py): a plain device copy, 16 bytes per lane, nontemporal -- the HBM rate a streaming kernel can
  * reach on this box, which SURVEY.md section 8(d) asks the bandwidth fractions to be read against.  bytes % 16 == 0. */
 int ss_tool_copy_fwd(const void* src, void* dst, long long bytes, ss_stream_t stream);

@@ -10,7 +10,8 @@
   visualization  the evaluation step's image outputs under the reference's names (utils/visualization.py, utils/mask_vis.py),
             install_visualization(script_module)
   data      the datasets' sample preparation on the device (datasets/us3d_.py, datasets/whu_dataset.py): normalised views, ground-truth
-            pyramids, gx / gy; RawStereoDataset and DeviceLoader
+            pyramids, gx / gy; right_view (right-view ground truth, the left view's visibility) and lr_consistency;
+            RawStereoDataset and DeviceLoader
   dist      one-process-per-GPU batch sharding (RCCL / gloo)
 
 The compute lives in csrc/libsemstereo_hip.so behind the C ABI of include/semstereo_hip.h.
@@ -23,6 +24,7 @@ from .metrics import EvalAverager, SegmentationMetric, disparity_metrics, eval_m
 from .joint_metrics import JointMetric, eval_metrics_joint  # noqa: F401  (the record itself: joint_metrics.joint_metrics)
 from .visualization import disp_error_image_func, eval_images, feature_vis, label_vis, normalize_image  # noqa: F401
 from .data import DeviceLoader, RawStereoDataset, image_gradients, nearest_pyramid, normalize_views, prepare_sample  # noqa: F401
+from .data import RIGHT_VIEW_KEYS, lr_consistency, right_view  # noqa: F401
 from .segment import GraphedSegment, HotSegment, PairPipeline  # noqa: F401
 
 __version__ = "0.1.0"

@@ -6,6 +6,8 @@ tensors per 1024 x 1024 item (tools/bench_data.py) -- from the 11 MB of raw arra
   nearest_pyramid    us3d_.py:178-182             the five cv2.resize(..., INTER_NEAREST) calls and the float32 label
   image_gradients    us3d_.py:98-109              gx / gy: three convert("L"), a float64 mean and std, two float64 convolve2d
   prepare_sample     us3d_.py:184-215             the sample dictionary with the reference's keys, per branch and per dataset
+  right_view         us3d_.py:115-133, :193       the commented-out forward warp: right-view label and disparity, the left view's visibility
+  lr_consistency     loss.py:121-135 (the idea)   the left-right check of two estimates, for inference without ground truth
   RawStereoDataset   us3d_.py:38-74               the list files and the decode (PIL only); no arithmetic on the host
   DeviceLoader                                    copies a raw batch from pinned memory on a side stream and prepares it there, one batch ahead
 
@@ -29,6 +31,14 @@ The arithmetic, defined once and used by both paths:
     ifx = 1.0 / (double(dst) / double(src)) in double, as OpenCV's resizeNN forms it; for H and W divisible by k that is d * k exactly.
     cv2 is not installed where this was written: for sizes that k does not divide, the formula is taken from OpenCV's source and is
     unverified.  The kernel takes H and W divisible by 16; other sizes take the composition.
+  * right view (csrc/right_view.hip; rows up to 8192 wide): per row, a left pixel x with a valid disparity (lo <= d < hi) lands on
+    right column t = round(float(x) - d), fp32, half to even, if 0 <= t < W; the largest x landing on a column owns it.  Selections
+    only, so both paths give the same bits; the kernel's owners are an integer maximum in LDS.  See right_view and lr_consistency.
+
+The right view in use, with m = maxdisp and `sample` from prepare_sample / DeviceLoader(keys=(..., "right_label", "left_visible"), maxdisp=m):
+    loss_r = F.cross_entropy(pred_label_r, sample["right_label"].long(), ignore_index=5)       # the right head on its own ground truth
+    noc = disparity_metrics(ests, sample["disparity"], maxdisp=m, mask_img=sample["left_visible"])   # "noc"; without mask_img: "all"
+    ok = lr_consistency(model(left, right), -model(right, left), threshold=1.0, maxdisp=m)      # without ground truth
 
 Departures from the reference: every entry is a tensor on the inputs' device (the reference returns numpy arrays for `disparity`, the
 pyramid levels and `label`, which the collate turns into the same tensors); the statistics are the exact-integer form above.
@@ -59,6 +69,9 @@ KEYS = {
     ("whu", False): ("left", "right", "disparity", "top_pad", "right_pad", "left_filename", "gx", "gy"),
 }
 _PASS_THROUGH = ("top_pad", "right_pad", "left_filename")
+#: what right_view adds to a sample when `keys` names it (no name starts with "disparity" or "label": those are pyramid levels)
+RIGHT_VIEW_KEYS = ("right_label", "right_disparity", "left_visible")
+MAX_RIGHT_VIEW_WIDTH = 8192                  # the owners of a row are 4 W bytes of LDS
 
 
 def view_table():
@@ -249,21 +262,155 @@ def image_gradients(left_u8):
     return _gradients_torch(left_u8 if left_u8.dtype == torch.uint8 else left_u8.clamp(0, 255).to(torch.uint8))
 
 
+# ------------------------------------------------------------------------------------------------ the right view
+def _disp_range(maxdisp, disp_range):
+    """(lo, hi) as the float32 values both paths compare against."""
+    assert (maxdisp is None) != (disp_range is None), "give exactly one of maxdisp (the signed range) and disp_range=(lo, hi)"
+    lo, hi = (-maxdisp, maxdisp) if disp_range is None else disp_range
+    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    assert lo < hi, "the disparity range is lo < hi"
+    return lo, hi
+
+
+def _label_for_kernel(label, disparity):
+    """(code, row stride, image stride) where the kernels read `label` in place, else None."""
+    if not (label.is_cuda and label.device == disparity.device and label.dtype in LABEL_CODES):
+        return None
+    B, H, W = label.shape
+    if label.stride(2) != 1 or label.stride(1) < W or (B > 1 and label.stride(0) < (H - 1) * label.stride(1) + W):
+        return None
+    return LABEL_CODES[label.dtype], label.stride(1), max(label.stride(0), (H - 1) * label.stride(1) + W)
+
+
+def _targets(d, lo, hi):
+    """(lands bool [B,H,W], target column int64 [B,H,W] with W where the pixel does not land, x int64 [1,1,W])."""
+    W = d.shape[-1]
+    x = torch.arange(W, device=d.device).view(1, 1, W)
+    t = torch.round(x.to(torch.float32) - d)
+    lands = (d >= lo) & (d < hi) & (t >= 0) & (t < W)
+    return lands, torch.where(lands, t, torch.full_like(t, W)).long(), x
+
+
+def _right_view_torch(d, label, lo, hi, fill_disparity, fill_label, want):
+    B, H, W = d.shape
+    lands, t, x = _targets(d, lo, hi)
+    owner = torch.full((B, H, W + 1), -1, dtype=torch.int64, device=d.device)       # the last slot collects what does not land
+    owner.scatter_reduce_(2, t, x.expand(B, H, W), "amax", include_self=True)
+    out = {}
+    if "right_disparity" in want or "right_label" in want:
+        own = owner[..., :W]
+        has, src = own >= 0, own.clamp(min=0)
+        if "right_disparity" in want:
+            out["right_disparity"] = torch.where(has, d.gather(2, src), torch.full_like(d, fill_disparity))
+        if "right_label" in want:
+            y = label.to(torch.float32)
+            out["right_label"] = torch.where(has, y.gather(2, src), torch.full_like(y, fill_label))
+    if "left_visible" in want:
+        out["left_visible"] = lands & (owner.gather(2, t) == x)
+    return out
+
+
+@_nograd
+def right_view(disparity, label=None, maxdisp=None, disp_range=None, fill_disparity=-999.0, fill_label=5.0,
+               want=RIGHT_VIEW_KEYS):
+    """The ground truth as the right camera sees it, and what of the left view it sees at all: the forward warp the reference left as
+    a commented-out per-pixel loop (us3d_.py:115-133, `"label_r"` at :193).  `disparity` [B,H,W] (or [H,W]) of the left view, float32
+    (anything else is converted first), a left pixel x matching right column x - d; `label` [B,H,W] of any dtype.  Exactly one of
+    `maxdisp` (valid: -maxdisp <= d < maxdisp, the range masks of main_us3d.py:199) and `disp_range=(lo, hi)` (valid: lo <= d < hi;
+    (0, maxdisp) for the unsigned variant).  Row by row:
+      * x LANDS on t = round(float(x) - d) (fp32, half to even) if d is valid and 0 <= t < W;
+      * the owner of a right column is the LARGEST x that lands on it -- the last writer of a raster-order loop and, the pixel further
+        right having the larger disparity up to the rounding step, the surface nearer the sensor;
+      * "right_disparity" = d[owner] and "right_label" = float(label[owner]), `fill_disparity` (-999, the dataset's no-data value)
+        and `fill_label` (5, the ignored class) where nothing lands; "left_visible" (bool) = x lands and owns its column -- the
+        non-occluded mask that disparity_metrics(mask_img=) and joint_metrics(mask=) take.
+    Nothing is interpolated, so the kernel (csrc/right_view.hip) and the composition agree bit for bit.  `want` names the entries to
+    compute; "right_label" needs a label.  Returns a dictionary of tensors on the input's device; nothing waits on the host."""
+    want = tuple(want)
+    assert want and set(want) <= set(RIGHT_VIEW_KEYS), f"want names some of {RIGHT_VIEW_KEYS}"
+    assert "right_label" not in want or label is not None, "right_label needs a label"
+    lo, hi = _disp_range(maxdisp, disp_range)
+    squeeze = disparity.dim() == 2
+    if squeeze:
+        disparity, label = disparity.unsqueeze(0), None if label is None else label.unsqueeze(0)
+    assert disparity.dim() == 3 and (label is None or label.shape == disparity.shape), "maps are [B,H,W]"
+    if "right_label" not in want:
+        label = None
+    B, H, W = disparity.shape
+    fill_disparity, fill_label = float(np.float32(fill_disparity)), float(np.float32(fill_label))
+    how = None if label is None else _label_for_kernel(label, disparity)
+    if (disparity.dtype == torch.float32 and _hip(disparity) and W <= MAX_RIGHT_VIEW_WIDTH and 0 < disparity.numel() < _MAX_ELEMENTS
+            and (label is None or how is not None)):
+        count("data_hip")
+        dev = disparity.device
+        out = {k: torch.empty((B, H, W), dtype=torch.bool if k == "left_visible" else torch.float32, device=dev) for k in want}
+        code, row, img = how if how is not None else (0, W, H * W)
+        with torch.cuda.device(dev):
+            call("ss_right_view_fwd", ptr(disparity), ptr(label), code, row, img, B, H, W, lo, hi, fill_disparity, fill_label,
+                 ptr(out.get("right_disparity")), ptr(out.get("right_label")), ptr(out.get("left_visible")))
+    else:
+        count("data_torch")
+        out = _right_view_torch(disparity.to(torch.float32), label, lo, hi, fill_disparity, fill_label, want)
+    out = {k: out[k] for k in want}
+    return {k: v[0] for k, v in out.items()} if squeeze else out
+
+
+@_nograd
+def lr_consistency(disp_left, disp_right, threshold=1.0, maxdisp=None, disp_range=None, return_diff=False):
+    """The left-right consistency check of two estimates, for inference without ground truth.  `disp_left` [B,H,W] (or [H,W]) in the
+    convention of right_view; `disp_right[r]` is the disparity of RIGHT pixel r, its left match at r + disp_right[r] -- the form
+    "right_disparity" has, and minus what the model returns for the swapped pair, `-model(right, left)`.  With t(x) as in right_view:
+    diff[x] = |disp_left[x] - disp_right[t(x)]| in fp32 where x lands and disp_right[t(x)] is valid, +inf elsewhere; the result is
+    the bool map diff <= threshold, or with `return_diff` the pair (that map, diff).  The range as in right_view."""
+    lo, hi = _disp_range(maxdisp, disp_range)
+    threshold = float(np.float32(threshold))
+    assert threshold >= 0, "the threshold is not negative"
+    squeeze = disp_left.dim() == 2
+    if squeeze:
+        disp_left, disp_right = disp_left.unsqueeze(0), disp_right.unsqueeze(0)
+    assert disp_left.dim() == 3 and disp_right.shape == disp_left.shape, "maps are [B,H,W]"
+    B, H, W = disp_left.shape
+    if (disp_left.dtype == torch.float32 and disp_right.dtype == torch.float32 and _hip(disp_left, disp_right)
+            and 0 < disp_left.numel() < _MAX_ELEMENTS):
+        count("data_hip")
+        dev = disp_left.device
+        ok = torch.empty((B, H, W), dtype=torch.bool, device=dev)
+        diff = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_diff else None
+        with torch.cuda.device(dev):
+            call("ss_lr_consistency_fwd", ptr(disp_left), ptr(disp_right), B, H, W, lo, hi, threshold, ptr(ok), ptr(diff))
+    else:
+        count("data_torch")
+        dl, dr = disp_left.to(torch.float32), disp_right.to(torch.float32)
+        lands, t, _ = _targets(dl, lo, hi)
+        m = dr.gather(2, t.clamp(max=W - 1))
+        found = lands & (m >= lo) & (m < hi)
+        diff = torch.where(found, (dl - m).abs(), torch.full_like(dl, float("inf")))
+        ok = diff <= threshold
+    if squeeze:
+        ok, diff = ok[0], None if diff is None else diff[0]
+    return (ok, diff) if return_diff else ok
+
+
 # ------------------------------------------------------------------------------------------------ the sample dictionary
 @_nograd
-def prepare_sample(raw, training, keys=None, disp_scale=None):
+def prepare_sample(raw, training, keys=None, disp_scale=None, maxdisp=None, disp_range=None):
     """The dictionary of the reference's `__getitem__` after the collate, from the raw arrays: `raw` holds "left_u8" and "right_u8"
     (uint8 [B,H,W,3]), "disparity" ([B,H,W] float32, or int32 as WHU's 16-bit files decode) and, for US3D, "label" ([B,H,W]); without a
     label the WHU key set is returned.  The training branch has the pyramids, the test branch "top_pad", "right_pad" (0 where `raw` has
     none) and "left_filename" (where `raw` has one), passed through.  `keys` selects a subset, and only what it names is computed: a
     training script reads "left", "right", "disparity", "disparity_4" and "label".  `disp_scale`: None = 1 / 256 for an integer
-    disparity (whu_dataset.py:36) and 1 for a floating one."""
+    disparity (whu_dataset.py:36) and 1 for a floating one.  `keys` may also name RIGHT_VIEW_KEYS -- "right_label" (US3D only),
+    "right_disparity", "left_visible": right_view of the float32 `disparity` entry (WHU: the scaled map) and the label, which needs
+    `maxdisp` or `disp_range`; they follow the reference's keys and are never part of the default dictionary."""
     kind = "us3d" if raw.get("label") is not None else "whu"
     names = KEYS[(kind, bool(training))]
     want = names if keys is None else tuple(k for k in names if k in set(keys))
+    views = ()
     if keys is not None:                                                         # (a name of the other branch is no error: one list serves both)
-        unknown = set(keys) - {k for v in KEYS.values() for k in v}
+        unknown = set(keys) - {k for v in KEYS.values() for k in v} - set(RIGHT_VIEW_KEYS)
         assert not unknown, f"not keys of any sample: {sorted(unknown)}"
+        views = tuple(k for k in RIGHT_VIEW_KEYS if k in set(keys) and (kind == "us3d" or k != "right_label"))
+        assert not views or (maxdisp is None) != (disp_range is None), f"{views} need exactly one of maxdisp and disp_range"
     disparity = raw["disparity"]
     if disp_scale is None:
         disp_scale = 1.0 if disparity.is_floating_point() else 1.0 / 256.0
@@ -281,6 +428,10 @@ def prepare_sample(raw, training, keys=None, disp_scale=None):
                               disp_levels=[int(k.split("_")[1]) for k in maps if k.startswith("disparity_")],
                               label_levels=[int(k.split("_")[1]) for k in labels if "_" in k], disp_scale=disp_scale)
         out.update({k: pyr[k] for k in maps})
+    if views:
+        d = out["disparity"] if "disparity" in out else _scaled(disparity, float(disp_scale))
+        out.update(right_view(d, raw["label"] if "right_label" in views else None, maxdisp=maxdisp, disp_range=disp_range, want=views))
+        want = want + views
     if "gx" in want or "gy" in want:
         gx, gy = image_gradients(raw["left_u8"])
         out.update({k: v for k, v in (("gx", gx), ("gy", gy)) if k in want})
@@ -337,12 +488,13 @@ class DeviceLoader:
     dictionaries on `device`.  On a CUDA device the raw batch is copied from pinned memory on a side stream and prepare_sample runs
     there, one batch ahead of the consumer; a batch is handed to the caller's current stream behind an event, with record_stream on
     every tensor handed out, so `sample['left'].cuda()` in the reference's train_sample is a no-op and the function runs as written.
-    `training`: None = the dataset's own flag."""
+    `training`: None = the dataset's own flag; `keys`, `disp_scale`, `maxdisp` and `disp_range` are prepare_sample's."""
 
-    def __init__(self, loader, device=None, keys=None, training=None, disp_scale=None):
+    def __init__(self, loader, device=None, keys=None, training=None, disp_scale=None, maxdisp=None, disp_range=None):
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.loader, self.device, self.keys, self.disp_scale = loader, torch.device(device), keys, disp_scale
+        self.range = {"maxdisp": maxdisp, "disp_range": disp_range}             # for the RIGHT_VIEW_KEYS that `keys` names
         if training is None:
             training = getattr(getattr(loader, "dataset", None), "training", True)
         self.training = bool(training)
@@ -362,12 +514,13 @@ class DeviceLoader:
 
     def _prepare(self, raw):
         if self.device.type != "cuda":
-            return prepare_sample(raw, self.training, self.keys, self.disp_scale), None
+            return prepare_sample(raw, self.training, self.keys, self.disp_scale, **self.range), None
         if self._stream is None:
             self._stream = torch.cuda.Stream(self.device)
             self._stream.wait_stream(torch.cuda.current_stream(self.device))    # (once: the table's upload is on the caller's stream)
         with torch.cuda.stream(self._stream):
-            sample = prepare_sample({k: self._upload(v) for k, v in raw.items()}, self.training, self.keys, self.disp_scale)
+            sample = prepare_sample({k: self._upload(v) for k, v in raw.items()}, self.training, self.keys, self.disp_scale,
+                                    **self.range)
             done = torch.cuda.Event()
             done.record(self._stream)
         return sample, done
