@@ -9,8 +9,10 @@
 // A GEMM with M = Cout, N = Cin per tap and K = every output position.  Both operands are rows of an NCDHW tensor, so "8
 // consecutive k per lane" -- what v_mfma_f32_32x32x16_bf16 wants of A (lane = output channel) and B (lane = input channel) -- are 8
 // consecutive W positions of one channel row: the natural layout.  fp32 is kept by the split of conv3d_bf16s.hip: x = hi + mid +
-// lo bf16 terms, six cross products, fp32 accumulation (error below the exact-fp32 MFMA's; bf16 has fp32's exponent range, so
-// gradients of any magnitude need no scaling).
+// lo bf16 terms, six cross products, fp32 accumulation (error of the size of the exact-fp32 MFMA's: measured on every region of
+// tests/test_wgrad_forms_gpu.py -- each tap, each channel tile -- between 0.2 and 2.5 times that kernel's, never above 1.5 times it
+// + 1e-6 of the region's largest value, profiles/wgrad_forms_err.txt; bf16 has fp32's exponent range, so gradients of any magnitude
+// need no scaling: the same file, grad_out times 2^-100 ... 2^40).
 //
 // Three kernels share that arithmetic (ss_conv3d_wgrad_bf16s_fwd picks): `conv3d_wgrad_bf16s_coop` for stride 1 (nine waves walk down a
 // column of chunks and share what they stage: the form every big layer runs, further down), `conv3d_wgrad_bf16s<S>` below for stride 2 and
@@ -34,11 +36,12 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_plan.h"
 #include "split_bf16.h"
 
 namespace {
 
-constexpr int CW = 32;                                    // output positions per chunk (two K-steps of 16)
+constexpr int CW = ss::kWgradChunk;                       // output positions per chunk (two K-steps of 16)
 template <int S>
 struct WG {
     // S = 1: one row [8 pad | 32 | 8 pad] bf16 per (term, ci): 96 bytes, stride 112; S = 2: rows E [32] and O [8 pad | 32]: stride 80
@@ -737,67 +740,39 @@ extern "C" int ss_conv3d_wgrad_bf16s_fwd(const float* grad_out, const float* in,
     hipStream_t st = ss::as_stream(stream);
     const int ci_tiles = ss::ceil_div(Cin, 32), tiles = ci_tiles * ss::ceil_div(Cout, 32);
     if (tiles > 65535) return SS_ERR_UNSUPPORTED;
-    if (Cout == 1 && stride == 1 && ss::tuning().wgrad_coop != 0) {
+    if ((long long)Do * Ho * ss::ceil_div(Wo, CW) > 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
+    // which kernel, and how its chunks are cut over the grid: ss::plan_wgrad3d (conv_plan.h)
+    const ss::WgradPlan p = ss::plan_wgrad3d(B, Cin, Cout, D, H, W, stride, ss::tuning().wgrad_coop != 0);
+    if (p.kernel == ss::WgradKernel::head) {
         // a single output channel: the taps as the matrix columns (conv3d_wgrad_head_bf16s), straight into grad_w
         if (hipMemsetAsync(grad_w, 0, (size_t)Cin * 27 * sizeof(float), st) != hipSuccess) return SS_ERR_LAUNCH;
-        const int cpr = ss::ceil_div(W, CW);
-        const long long total_ll = (long long)D * H * cpr;
-        if (total_ll > 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
-        const int total = (int)total_ll;
-        const int waves = std::max(4, 2048 / (ci_tiles * B));
-        const int per_wave = std::max(1, ss::ceil_div(total, waves));
-        const int nwaves = ss::ceil_div(total, per_wave);
-        hipLaunchKernelGGL(conv3d_wgrad_head_bf16s, dim3(ss::ceil_div(nwaves, 4), ci_tiles, B), dim3(256), 0, st, grad_out, in, grad_w, Cin, D, H, W,
-                           cpr, total, per_wave);
+        hipLaunchKernelGGL(conv3d_wgrad_head_bf16s, dim3(ss::ceil_div(p.nwaves, 4), ci_tiles, B), dim3(256), 0, st, grad_out, in, grad_w, Cin, D, H, W,
+                           p.chunks_per_row, p.total_chunks, p.per_wave);
         return ss::check_launch();
     }
     if (hipMemsetAsync(workspace, 0, (size_t)tiles * 27 * 1024 * sizeof(float), st) != hipSuccess) return SS_ERR_LAUNCH;
-    const int chunks_per_row = ss::ceil_div(Wo, CW);
-    const long long total_ll = (long long)Do * Ho * chunks_per_row;
-    if (total_ll > 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
-    const int total = (int)total_ll;
-    // ~8 waves per CU on 256 CUs; a unit (= wave) is (kernel-depth plane, tile pair, batch element, chunk range)
-    int nsplit = std::max(1, 3072 / (9 * tiles * B));             // ~12 waves per CU on 256 CUs
-    int per_unit = std::max(chunks_per_row >= 4 ? 4 : 1, ss::ceil_div(total, nsplit));
-    nsplit = ss::ceil_div(total, per_unit);
-    const dim3 grid(ss::ceil_div(nsplit, 8) * 24, tiles, B);          // (split, kd) -> block index ((split / 8) * 3 + kd) * 8 + split % 8
-    if (stride == 1 && ss::tuning().wgrad_coop != 0) {
-        // the cooperative form: a workgroup walks down a column (od, w0) of chunks, the columns cut into segments so that ~3 workgroups
-        // per CU exist
+    const dim3 grid(ss::ceil_div(p.nsplit, 8) * 24, tiles, B);        // (split, kd) -> block index ((split / 8) * 3 + kd) * 8 + split % 8
+    if (p.kernel == ss::WgradKernel::coop) {
         auto kern = conv3d_wgrad_bf16s_coop;
         if (ss::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), CO_LDS) != SS_OK) return SS_ERR_LAUNCH;
-        const long long cols = (long long)Do * chunks_per_row;
-#ifndef SS_COOP_WGS
-#define SS_COOP_WGS 768
-#endif
-        int nseg_c = (int)std::min<long long>(std::max<long long>(1, SS_COOP_WGS / std::max<long long>(1, cols * tiles * B)), std::max(1, Ho / 8));
-        const int seg_len = ss::ceil_div(Ho, nseg_c);
-        nseg_c = ss::ceil_div(Ho, seg_len);
-        if (cols * nseg_c > 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(cols * nseg_c), tiles, B), dim3(576), CO_LDS, st, grad_out, in, workspace, Cin, Cout, D, H, W,
-                           chunks_per_row, seg_len, nseg_c, ci_tiles);
-    } else if (stride == 1) {
+        const long long cols = (long long)Do * p.chunks_per_row;
+        if (cols * p.nseg > 0x7fffffffLL) return SS_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(cols * p.nseg), tiles, B), dim3(576), CO_LDS, st, grad_out, in, workspace, Cin, Cout, D, H, W,
+                           p.chunks_per_row, p.seg_len, p.nseg, ci_tiles);
+    } else if (p.kernel == ss::WgradKernel::per_wave_s1) {
         auto kern = conv3d_wgrad_bf16s<1>;
-        hipLaunchKernelGGL(kern, grid, dim3(192), 3 * WG<1>::TILE, st, grad_out, in, workspace, Cin, Cout, D, H, W, Do, Ho, Wo, chunks_per_row,
-                           total, per_unit, nsplit, ci_tiles);
-    } else if (ss::tuning().wgrad_coop != 0) {
-        // stride 2 with the gout chunk shared: a workgroup = the nine kernel rows of a chunk range; ONE workgroup per CU's worth of ranges (each
-        // ends with 27 648 atomics into the workspace: 768 ranges 234 us, 256 ranges 203, 3072 ranges 368 on hourglass.conv1's layer)
+        hipLaunchKernelGGL(kern, grid, dim3(192), 3 * WG<1>::TILE, st, grad_out, in, workspace, Cin, Cout, D, H, W, Do, Ho, Wo, p.chunks_per_row,
+                           p.total_chunks, p.per_unit, p.nsplit, ci_tiles);
+    } else if (p.kernel == ss::WgradKernel::s2a) {
         auto kern = conv3d_wgrad_bf16s_s2a;
         if (ss::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), S2A_LDS) != SS_OK) return SS_ERR_LAUNCH;
-#ifndef SS_S2A_WGS
-#define SS_S2A_WGS 256
-#endif
-        int ns = std::max(1, SS_S2A_WGS / (tiles * B));
-        int pu = std::max(chunks_per_row >= 4 ? 4 : 1, ss::ceil_div(total, ns));
-        ns = ss::ceil_div(total, pu);
-        hipLaunchKernelGGL(kern, dim3(ns, tiles, B), dim3(576), S2A_LDS, st, grad_out, in, workspace, Cin, Cout, D, H, W, Do, Ho, Wo, chunks_per_row,
-                           total, pu, ci_tiles);
+        hipLaunchKernelGGL(kern, dim3(p.ns, tiles, B), dim3(576), S2A_LDS, st, grad_out, in, workspace, Cin, Cout, D, H, W, Do, Ho, Wo, p.chunks_per_row,
+                           p.total_chunks, p.pu, ci_tiles);
     } else {
         auto kern = conv3d_wgrad_bf16s<2>;
         if (ss::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 3 * WG<2>::TILE) != SS_OK) return SS_ERR_LAUNCH;
-        hipLaunchKernelGGL(kern, grid, dim3(192), 3 * WG<2>::TILE, st, grad_out, in, workspace, Cin, Cout, D, H, W, Do, Ho, Wo, chunks_per_row,
-                           total, per_unit, nsplit, ci_tiles);
+        hipLaunchKernelGGL(kern, grid, dim3(192), 3 * WG<2>::TILE, st, grad_out, in, workspace, Cin, Cout, D, H, W, Do, Ho, Wo, p.chunks_per_row,
+                           p.total_chunks, p.per_unit, p.nsplit, ci_tiles);
     }
     if (ss::check_launch() != SS_OK) return SS_ERR_LAUNCH;
     const long long n = (long long)Cout * Cin * 27;

@@ -1,5 +1,5 @@
-// The ONE statement of the conv launchers' tile and accumulation rule (conv3d_bf16s.hip, conv3d_gather.hip, conv3d_classifier.hip)
-// and of the transposed convs' form rule (deconv3d_bf16s.hip):
+// The ONE statement of the conv launchers' tile and accumulation rule (conv3d_bf16s.hip, conv3d_gather.hip, conv3d_classifier.hip),
+// of the transposed convs' form rule (deconv3d_bf16s.hip) and of the 3x3x3 weight gradients' kernel and partition rule (conv3d_wgrad_bf16s.hip):
 // pure functions of integers, host-only, nothing from HIP.  Callers pass ss::fill_hint() and ss::tuning() in.
 #pragma once
 #ifndef SS_S2_MS_MIN_WGS
@@ -98,5 +98,75 @@ constexpr DeconvPlan plan_deconv3d(int D, int H, int W, int Cout, int B, int nte
     // outputs are handed to the next kernel by the 256 MB Infinity Cache); SS_DECONV_STREAM=0/1 forces it.
     const bool stream = forced_stream >= 0 ? forced_stream != 0 : (long long)B * Cout * 8 * D * H * W * 4 >= kDeconvStreamBytes;
     return {tile, groups, groups == 0 && stream};
+}
+
+// ---- the weight gradients of the 3x3x3 convs (conv3d_wgrad_bf16s.hip): which kernel, and how its K range (every output position, walked
+// in chunks of kWgradChunk positions of one output row) is cut over the grid ----
+#ifndef SS_COOP_WGS
+#define SS_COOP_WGS 768           // cooperative stride-1 form: workgroups aimed at (~3 per CU) when a column of chunks is cut into segments
+#endif
+#ifndef SS_S2A_WGS
+#define SS_S2A_WGS 256            // shared-gout stride-2 form: ONE workgroup per CU's worth of chunk ranges
+#endif
+constexpr int kWgradChunk = 32;           // output positions per chunk (two K-steps of 16)
+enum class WgradKernel { coop, per_wave_s1, s2a, per_wave_s2, head };
+// The fields a kernel does not launch by are 0.
+//   every kernel: chunks_per_row, total_chunks (Do x Ho rows of chunks_per_row);  ci_tiles x co_tiles = tiles of 32 x 32 channels
+//   per_wave_s1 / per_wave_s2: nsplit chunk ranges of per_unit chunks; the grid has ceil(nsplit / 8) * 24 blocks (split, kd) -> block
+//                              ((split / 8) * 3 + kd) * 8 + split % 8, those with split >= nsplit leave
+//   coop: a column (od, w0) of chunks is cut into nseg segments of seg_len output rows
+//   s2a:  ns chunk ranges of pu chunks
+//   head: nwaves waves of per_wave chunks, four to a workgroup
+struct WgradPlan {
+    WgradKernel kernel;
+    int ci_tiles, tiles, chunks_per_row, total_chunks, per_unit, nsplit, nseg, seg_len, ns, pu, per_wave, nwaves;
+};
+
+constexpr long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+constexpr long long imax(long long a, long long b) { return a > b ? a : b; }
+constexpr long long imin(long long a, long long b) { return a < b ? a : b; }
+
+// (D, H, W): the INPUT's extents (the output's are (N - 1) / stride + 1); coop: ss::tuning().wgrad_coop != 0.  The caller has checked
+// that the chunk count fits an int.
+constexpr WgradPlan plan_wgrad3d(int B, int Cin, int Cout, int D, int H, int W, int stride, bool coop) {
+    const int Do = (D - 1) / stride + 1, Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    WgradPlan p{};
+    p.ci_tiles = (int)cdiv(Cin, 32);
+    p.tiles = p.ci_tiles * (int)cdiv(Cout, 32);
+    p.chunks_per_row = (int)cdiv(Wo, kWgradChunk);
+    const long long total = (long long)Do * Ho * p.chunks_per_row;
+    p.total_chunks = (int)total;
+    if (Cout == 1 && stride == 1 && coop) {
+        // a single output channel: the taps as the matrix columns, ~2048 waves
+        p.kernel = WgradKernel::head;
+        const long long waves = imax(4, 2048 / ((long long)p.ci_tiles * B));
+        p.per_wave = (int)imax(1, cdiv(total, waves));
+        p.nwaves = (int)cdiv(total, p.per_wave);
+        return p;
+    }
+    const int floor_chunks = p.chunks_per_row >= 4 ? 4 : 1;
+    if (stride == 1 && coop) {
+        // the cooperative form: a workgroup walks down a column (od, w0) of chunks, the columns cut into segments so that ~3 workgroups
+        // per CU exist
+        p.kernel = WgradKernel::coop;
+        const long long cols = (long long)Do * p.chunks_per_row;
+        const long long nseg = imin(imax(1, SS_COOP_WGS / imax(1, cols * p.tiles * B)), imax(1, Ho / 8));
+        p.seg_len = (int)cdiv(Ho, nseg);
+        p.nseg = (int)cdiv(Ho, p.seg_len);
+    } else if (stride == 2 && coop) {
+        // stride 2 with the gout chunk shared: a workgroup = the nine kernel rows of a chunk range; ONE workgroup per CU's worth of ranges (each
+        // ends with 27 648 atomics into the workspace: 768 ranges 234 us, 256 ranges 203, 3072 ranges 368 on hourglass.conv1's layer)
+        p.kernel = WgradKernel::s2a;
+        const long long ns = imax(1, SS_S2A_WGS / ((long long)p.tiles * B));
+        p.pu = (int)imax(floor_chunks, cdiv(total, ns));
+        p.ns = (int)cdiv(total, p.pu);
+    } else {
+        // one wave = one unit (kernel-depth plane, kernel row, tile pair, batch element, chunk range): ~12 waves per CU on 256 CUs
+        p.kernel = stride == 1 ? WgradKernel::per_wave_s1 : WgradKernel::per_wave_s2;
+        const long long nsplit = imax(1, 3072 / (9LL * p.tiles * B));
+        p.per_unit = (int)imax(floor_chunks, cdiv(total, nsplit));
+        p.nsplit = (int)cdiv(total, p.per_unit);
+    }
+    return p;
 }
 }  // namespace ss

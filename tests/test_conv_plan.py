@@ -8,7 +8,10 @@ header is compiled with the system c++ and called through ctypes.
   * both sides of every threshold, the forced tile, the depth rule of the 4-row tile, one plan for the plain and the gather entry;
   * the transposed convs' form rule (ss::plan_deconv3d, what deconv3d_bf16s.hip launches by): its restatement _deconv_form of
     tests/test_f16_ranges_gpu.py on a grid across every threshold and every value of SS_DECONV_GROUPS and SS_DECONV_STREAM, and the
-    forms of the four transposed convs of the 1024^2 pair.
+    forms of the four transposed convs of the 1024^2 pair;
+  * the weight gradients' kernel and partition rule (ss::plan_wgrad3d, what conv3d_wgrad_bf16s.hip launches by): its restatement
+    _wgrad_form of tests/test_wgrad_forms_gpu.py on a grid across every threshold, on every case of that file and on the
+    CONV_TRAIN_CASES of tests/test_parity_gpu.py.
 """
 import ctypes
 import itertools
@@ -20,6 +23,8 @@ import torch
 
 import test_f16_ranges_gpu as fr
 import test_fill_hint_gpu as fh
+import test_parity_gpu as tp
+import test_wgrad_forms_gpu as wf
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "semstereo_amd", "csrc")
 PROBE = """
@@ -38,6 +43,13 @@ void probe_deconv3d(int D, int H, int W, int Cout, int B, int nterms, int forced
     out[0] = p.tile == ss::DeconvTile::t2x2x32 ? 2 : 1; out[1] = p.tile == ss::DeconvTile::t2x2x32 ? 2 : 4; out[2] = p.groups; out[3] = p.stream;
 }
 long long probe_deconv_stream_bytes() { return ss::kDeconvStreamBytes; }
+void probe_wgrad3d(int B, int Cin, int Cout, int D, int H, int W, int stride, int coop, int* out) {
+    const ss::WgradPlan p = ss::plan_wgrad3d(B, Cin, Cout, D, H, W, stride, coop != 0);
+    const int v[13] = {(int)p.kernel, p.ci_tiles, p.tiles, p.chunks_per_row, p.total_chunks, p.per_unit, p.nsplit, p.nseg, p.seg_len, p.ns, p.pu,
+                       p.per_wave, p.nwaves};
+    for (int i = 0; i < 13; ++i) out[i] = v[i];
+}
+int probe_wgrad_constant(int which) { return which == 0 ? SS_COOP_WGS : (which == 1 ? SS_S2A_WGS : ss::kWgradChunk); }
 }
 """
 TILES = ("4x4x32", "2x8x32", "1x8x32", "1x4x32")          # enum Tile3
@@ -263,3 +275,93 @@ def test_deconv_forms_of_the_1024_pair(probe):
             assert deconv_plan(probe, *shape, B) == ((1, 4), groups, streams), (name, B)
     assert deconv_plan(probe, 12, 128, 128, 32, 1)[2] and not deconv_plan(probe, 6, 64, 64, 64, 1)[2]
     assert deconv_plan(probe, 6, 64, 64, 64, 4)[2] and not deconv_plan(probe, 8, 32, 32, 64, 64)[2]
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# the 3x3x3 weight gradients: ss::plan_wgrad3d
+# --------------------------------------------------------------------------------------------------------------------
+
+WGRAD_KERNELS = ("coop", "per_wave_s1", "s2a", "per_wave_s2", "head")         # enum WgradKernel, under the names _wgrad_form uses
+WGRAD_FIELDS = ("kernel", "ci_tiles", "tiles", "chunks_per_row", "total_chunks", "per_unit", "nsplit", "nseg", "seg_len", "ns", "pu", "per_wave", "nwaves")
+
+
+def wgrad_plan(lib, B, Cin, Cout, D, H, W, stride, coop=True):
+    """-> the dict of wf._wgrad_form"""
+    r = (ctypes.c_int * 13)()
+    lib.probe_wgrad3d(B, Cin, Cout, D, H, W, stride, int(coop), r)
+    return dict(zip(WGRAD_FIELDS, (WGRAD_KERNELS[r[0]],) + tuple(r[1:])))
+
+
+# (B, Cin, Cout, D, H, W, stride) either side of each threshold of the rule:
+#   Cout 1 | 2 (the head kernel);  Wo 96 | 97 (three | four chunks per row: the floor of 4 chunks per range), at stride 2 W 192 | 193;
+#   per-wave: 3072 / (9 tiles B) = 341 ranges at one tile: 341 | 342 chunks (ranges of 1 | 2), 170 at two tiles, 0 -> 1 from 342 tiles x pairs;
+#   cooperative: 768 / (columns x tiles x B) against Ho / 8: 384 | 385 columns (2 | 1 segments), 768 | 769, Ho 15 | 16 | 17 | 24;
+#   shared gout: 256 / (tiles B) ranges: 256 | 257 chunks, 128 | 129 at two tiles, 0 -> 1 from 257 tiles x pairs;
+#   head: 2048 / (ci_tiles B) waves, at least 4: 2048 | 2049 chunks, B = 512 | 513, two channel tiles
+WGRAD_EDGES = [(1, 32, 1, 2, 3, 32, 1), (1, 32, 2, 2, 3, 32, 1), (1, 32, 1, 2, 3, 32, 2), (1, 32, 32, 1, 4, 96, 1), (1, 32, 32, 1, 4, 97, 1),
+               (1, 32, 32, 2, 4, 192, 2), (1, 32, 32, 2, 4, 193, 2), (1, 32, 32, 11, 31, 32, 1), (1, 32, 32, 9, 38, 32, 1), (1, 32, 33, 10, 17, 32, 1),
+               (1, 32, 33, 9, 19, 32, 1), (342, 32, 32, 2, 2, 32, 1), (341, 32, 32, 2, 2, 32, 1), (1, 32, 32, 12, 16, 32 * 32, 1),
+               (1, 32, 32, 11, 16, 32 * 35, 1), (1, 32, 32, 24, 64, 32 * 32, 1), (1, 32, 32, 769, 64, 32, 1), (1, 32, 32, 2, 15, 64, 1),
+               (1, 32, 32, 2, 16, 64, 1), (1, 32, 32, 2, 17, 64, 1), (1, 32, 32, 2, 24, 64, 1), (1, 32, 32, 31, 16, 64, 2), (1, 32, 32, 2, 257 * 2, 64, 2),
+               (1, 32, 64, 16, 16, 64, 2), (1, 32, 64, 2, 129 * 2, 64, 2), (128, 32, 32, 2, 8, 64, 2), (129, 32, 32, 2, 8, 64, 2), (170, 32, 32, 2, 2, 32, 1), (171, 32, 32, 2, 2, 32, 1),
+               (1, 32, 1, 32, 64, 32, 1), (1, 32, 1, 1, 2049, 32, 1), (512, 32, 1, 1, 5, 32, 1), (513, 32, 1, 1, 5, 32, 1), (1, 64, 1, 16, 64, 32, 1),
+               (1, 64, 1, 1, 1025, 32, 1), (1, 1, 1, 1, 1, 1, 1), (1, 1, 1, 1, 1, 1, 2), (3, 1, 2, 1, 1, 1, 2)]
+
+
+def test_wgrad_restatement_gives_the_headers_answers(probe):
+    assert [probe.probe_wgrad_constant(i) for i in range(3)] == [768, 256, 32]
+    shapes = list(WGRAD_EDGES) + list(wf.ENTRIES) + list(tp.CONV_TRAIN_CASES)
+    assert len(tp.CONV_TRAIN_CASES) == 11 and len(wf.ENTRIES) == 7 + 8 + 4 + 2
+    shapes += [(B, Cin, Cout, D, H, W, stride) for B, Cin, Cout, D, H, W, stride in itertools.product(
+        (1, 2, 3, 513), (1, 32, 33, 96), (1, 2, 32, 33, 64), (1, 2, 3, 12), (1, 7, 8, 15, 16, 17, 64), (1, 31, 32, 33, 96, 97, 129, 193, 257), (1, 2))]
+    for shape, coop in itertools.product(shapes, (True, False)):
+        assert wgrad_plan(probe, *shape, coop) == wf._wgrad_form(*shape, coop), (shape, coop)
+
+
+def test_wgrad_both_sides_of_every_threshold(probe):
+    live = lambda *a, **k: {n: v for n, v in wgrad_plan(probe, *a, **k).items() if v and n not in ("ci_tiles", "tiles")}      # noqa: E731
+    # which kernel: a single output channel at stride 1 is the head's, unless SS_WGRAD_COOP=0; the stride and the switch decide the rest
+    assert live(1, 32, 1, 2, 3, 32, 1) == dict(kernel="head", chunks_per_row=1, total_chunks=6, per_wave=1, nwaves=6)
+    assert live(1, 32, 1, 2, 3, 32, 1, coop=False)["kernel"] == "per_wave_s1" and live(1, 32, 1, 2, 3, 32, 2)["kernel"] == "s2a"
+    assert [live(1, 32, 2, 2, 3, 32, s, coop=c)["kernel"] for s, c in ((1, True), (1, False), (2, True), (2, False))] == list(WGRAD_KERNELS[:4])
+    # the floor of 4 chunks per range from four chunks per row: Wo 96 | 97 (per-wave form), W 192 | 193 at stride 2 (both forms)
+    assert live(1, 32, 32, 1, 4, 96, 1, coop=False) == dict(kernel="per_wave_s1", chunks_per_row=3, total_chunks=12, per_unit=1, nsplit=12)
+    assert live(1, 32, 32, 1, 4, 97, 1, coop=False) == dict(kernel="per_wave_s1", chunks_per_row=4, total_chunks=16, per_unit=4, nsplit=4)
+    assert live(1, 32, 32, 2, 4, 192, 2) == dict(kernel="s2a", chunks_per_row=3, total_chunks=6, ns=6, pu=1)
+    assert live(1, 32, 32, 2, 4, 193, 2) == dict(kernel="s2a", chunks_per_row=4, total_chunks=8, ns=2, pu=4)
+    assert live(1, 32, 32, 2, 4, 193, 2, coop=False) == dict(kernel="per_wave_s2", chunks_per_row=4, total_chunks=8, per_unit=4, nsplit=2)
+    # per-wave: 3072 / 9 = 341 ranges of one tile pair: 341 | 342 chunks; two tiles: 170 ranges, 170 | 171 chunks; 170 | 171 pairs: two ranges | one
+    assert live(1, 32, 32, 11, 31, 32, 1, coop=False) == dict(kernel="per_wave_s1", chunks_per_row=1, total_chunks=341, per_unit=1, nsplit=341)
+    assert live(1, 32, 32, 9, 38, 32, 1, coop=False) == dict(kernel="per_wave_s1", chunks_per_row=1, total_chunks=342, per_unit=2, nsplit=171)
+    assert live(1, 32, 33, 10, 17, 32, 1, coop=False)["per_unit"] == 1 and live(1, 32, 33, 9, 19, 32, 1, coop=False)["per_unit"] == 2
+    assert live(341, 32, 32, 2, 2, 32, 1, coop=False)["nsplit"] == 1 and live(342, 32, 32, 2, 2, 32, 1, coop=False)["nsplit"] == 1
+    assert live(170, 32, 32, 2, 2, 32, 1, coop=False)["nsplit"] == 2 and live(171, 32, 32, 2, 2, 32, 1, coop=False)["nsplit"] == 1
+    # cooperative: min(768 / (columns tiles B), Ho / 8) segments, of equal length rounded up
+    assert live(1, 32, 32, 12, 16, 32 * 32, 1) == dict(kernel="coop", chunks_per_row=32, total_chunks=12 * 16 * 32, nseg=2, seg_len=8)       # 384 columns
+    assert live(1, 32, 32, 11, 16, 32 * 35, 1) == dict(kernel="coop", chunks_per_row=35, total_chunks=11 * 16 * 35, nseg=1, seg_len=16)      # 385
+    assert live(1, 32, 32, 24, 64, 32 * 32, 1)["nseg"] == 1 and live(1, 32, 32, 769, 64, 32, 1)["nseg"] == 1                              # 768 | 769
+    assert [(lambda f: (f["nseg"], f["seg_len"]))(live(1, 32, 32, 2, H, 64, 1)) for H in (15, 16, 17, 24)] == [(1, 15), (2, 8), (2, 9), (3, 8)]
+    assert live(2, 32, 33, 2, 64, 64, 1)["nseg"] == 8 and live(2, 32, 33, 2, 64, 64, 1)["seg_len"] == 8                                    # 16 columns-tiles-pairs: 48, Ho / 8 decides
+    # shared gout: 256 / (tiles B) ranges
+    assert live(1, 32, 32, 31, 16, 64, 2) == dict(kernel="s2a", chunks_per_row=1, total_chunks=128, ns=128, pu=1)
+    assert live(1, 32, 32, 2, 257 * 2, 64, 2) == dict(kernel="s2a", chunks_per_row=1, total_chunks=257, ns=129, pu=2)
+    assert live(1, 32, 32, 2, 256 * 2, 64, 2)["pu"] == 1 and live(1, 32, 64, 2, 128 * 2, 64, 2)["pu"] == 1 and live(1, 32, 64, 2, 129 * 2, 64, 2)["pu"] == 2
+    assert live(128, 32, 32, 2, 8, 64, 2)["ns"] == 2 and live(129, 32, 32, 2, 8, 64, 2)["ns"] == 1           # four chunks: 256 / B = 2 | 1 ranges
+    # head: max(4, 2048 / (ci_tiles B)) waves
+    assert live(1, 32, 1, 32, 64, 32, 1) == dict(kernel="head", chunks_per_row=1, total_chunks=2048, per_wave=1, nwaves=2048)
+    assert live(1, 32, 1, 1, 2049, 32, 1) == dict(kernel="head", chunks_per_row=1, total_chunks=2049, per_wave=2, nwaves=1025)
+    assert live(1, 64, 1, 16, 64, 32, 1)["per_wave"] == 1 and live(1, 64, 1, 1, 1025, 32, 1)["per_wave"] == 2
+    assert live(512, 32, 1, 1, 5, 32, 1)["per_wave"] == 2 and live(513, 32, 1, 1, 5, 32, 1)["per_wave"] == 2 and live(513, 32, 1, 1, 4, 32, 1)["per_wave"] == 1
+    assert live(1024, 32, 1, 1, 8, 32, 1)["nwaves"] == 4 and live(1024, 32, 1, 1, 9, 32, 1)["nwaves"] == 3
+
+
+def test_wgrad_forms_of_the_training_cases(probe):
+    """which kernel each of the eleven CONV_TRAIN_CASES of tests/test_parity_gpu.py runs, and by what partition: stated here, so that a
+    retune that moves them shows"""
+    got = [wgrad_plan(probe, *c) for c in tp.CONV_TRAIN_CASES]
+    assert [g["kernel"] for g in got] == ["coop", "s2a", "coop", "coop", "s2a", "coop", "s2a", "head", "coop", "coop", "s2a"]
+    assert [(g["nseg"], g["seg_len"]) for g in got if g["kernel"] == "coop"] == [(1, 10), (1, 7), (1, 6), (2, 11), (8, 8), (4, 8)]
+    assert [(g["ns"], g["pu"]) for g in got if g["kernel"] == "s2a"] == [(12, 1), (6, 1), (50, 2), (64, 4)]
+    assert (got[7]["per_wave"], got[7]["nwaves"]) == (1, 81)
+    for c in tp.CONV_TRAIN_CASES:
+        assert wgrad_plan(probe, *c, coop=False) == wf._wgrad_form(*c, False)
