@@ -882,6 +882,37 @@ int ss_right_view_fwd(const float* disparity, const void* label, int label_dtype
  * consistent or diff may be NULL, not both.  A negative or NaN threshold, lo >= hi or a NaN range: -1.  2^31 or more elements: -2. */
 int ss_lr_consistency_fwd(const float* disp_left, const float* disp_right, int B, int H, int W, float lo, float hi, float threshold,
                           unsigned char* consistent, float* diff, ss_stream_t stream);
+/* ---- scene inference: tile windows and the feathered mosaic, csrc/scene_tiles.hip ----
+ * What stands around the model call when the input is a scene and not a tile.  The reference has nothing of the kind (its evaluation
+ * loader carries top_pad / right_pad keys that are always 0).
+ *   window   tile i of th x tw pixels at origin (oy, ox), anywhere: it may overhang the scene
+ *   weights  per axis w(i) = min(i + 1, T - i, R) for window-local index i, tile size T and ramp R: integers, never below 1; a tile
+ *            pixel weighs float(wy(iy)) * float(wx(ix))
+ *   blend    per mosaic pixel over the covering RESIDENT tiles in ascending (ty, tx): num = num + w * v, den = den + w, every product
+ *            and sum rounded to fp32, out = num / den with one IEEE division; under ONE tile out = v, the tile's own value (not
+ *            (w * v) / w, which rounds twice)
+ * ss_tile_views_fwd cuts the windows of a scene pair and applies ToTensor + Normalize in the same pass: left, right uint8 [H,W,3],
+ * origins int32 [n][2] as (y, x) in DEVICE memory, table as ss_prep_views_fwd takes it -> out_left, out_right float32 [n,3,th,tw],
+ * out[i][c][y][x] = table[c][scene[oy + y][ox + x][c]] inside the scene and 0.0f off it (the mean colour in normalised space).  right
+ * and out_right may both be NULL (one view).  n, th, tw, H or W <= 0: -1.  A tensor of 2^31 or more elements: -2. */
+int ss_tile_views_fwd(const unsigned char* left, const unsigned char* right, const int* origins, const float* table, int n, int th,
+                      int tw, int H, int W, float* out_left, float* out_right, ss_stream_t stream);
+/* Gathers finished tiles into rows y0 <= y < y1 of the mosaic; no other row is written.  disp_tiles, logit_tiles: DEVICE tables of
+ * nty * ntx addresses, tile (ty, tx) at ty * ntx + tx: its disparity float32 [th,tw] and its logits float32 [C,th,tw], read in place
+ * (a batch of tiles is data_ptr() + b * stride); entry 0 = not resident, the tile is skipped.  origin_y [nty], origin_x [ntx]: int32
+ * in DEVICE memory, ascending.  ry, rx: the ramps.  Per pixel, with the blend above:
+ *   disparity [H,W]    num / den of the tiles' disparities
+ *   logits    [C,H,W]  the same per channel
+ *   label     [H,W]    uint8, the lowest index of the largest blended logit (np.argmax's rule; a NaN counts as the maximum)
+ *   spread    [H,W]    max - min of the covering tiles' disparities: 0 under one tile, the seam diagnostic
+ *   count     [H,W]    uint8, the number of covering tiles
+ * Any output may be NULL and is then skipped, at least one is required; logits and label need logit_tiles, which is NULL exactly when
+ * C is 0.  The order is fixed and nothing is atomic: two calls give the same bits.  Every tile pixel is read once.  A pixel of the
+ * range that no resident tile covers gets 0 / 0.  A NULL required pointer, th or tw <= 0, ry or rx < 1, y0 > y1 or a range outside
+ * [0, H]: -1.  C > 8, more than 256 windows on an axis, 2^31 or more elements in a tile or in an output: -2. */
+int ss_tile_blend_fwd(const long long* disp_tiles, const long long* logit_tiles, const int* origin_y, const int* origin_x, int nty,
+                      int ntx, int th, int tw, int C, int ry, int rx, int H, int W, int y0, int y1, float* disparity, float* logits,
+                      unsigned char* label, float* spread, unsigned char* count, ss_stream_t stream);
 /* Measurement aid (bench.py): a plain device copy, 16 bytes per lane, nontemporal -- the HBM rate a streaming kernel can
  * reach on this box, which SURVEY.md section 8(d) asks the bandwidth fractions to be read against.  bytes % 16 == 0. */
 int ss_tool_copy_fwd(const void* src, void* dst, long long bytes, ss_stream_t stream);

@@ -15,7 +15,7 @@
 
 namespace {
 
-using namespace ss::stream;    // BLOCK, grid_for, aligned_to, block_sum, RowQuad, row_quad, store4
+using namespace ss::stream;    // BLOCK, grid_for, aligned_to, block_sum, RowQuad, row_quad, load_rgb4, rgb_byte, store4
 using ss::metrics::LT_I64;     // label sources: the codes of every label_dtype
 using ss::metrics::LT_U8;
 using ss::metrics::LT_F32;
@@ -27,20 +27,6 @@ constexpr int MAX_STAT_GROUPS = 1024;    // workgroups (and partial sums) per im
 
 typedef unsigned long long u64;
 typedef unsigned char u8;
-
-// 4 interleaved RGB pixels (12 bytes) at p as three little-endian words: three dword loads, or 3 nv byte loads (the rest zero)
-__device__ __forceinline__ void load_rgb4(const u8* p, int nv, unsigned (&w)[3]) {
-    if (nv == 4 && aligned_to(p, 4)) {
-        const unsigned* q = reinterpret_cast<const unsigned*>(p);
-        w[0] = q[0], w[1] = q[1], w[2] = q[2];
-    } else {
-        w[0] = w[1] = w[2] = 0u;
-#pragma unroll
-        for (int k = 0; k < 12; ++k)
-            if (k < 3 * nv) w[k >> 2] |= (unsigned)p[k] << (8 * (k & 3));
-    }
-}
-__device__ __forceinline__ unsigned rgb_byte(const unsigned (&w)[3], int k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
 
 // ---------------------------------------------------------------- views (datasets/data_io.py:6-13)
 struct ViewArgs {

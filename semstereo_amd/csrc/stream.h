@@ -1,4 +1,4 @@
-// What the streaming kernels share (loss.hip, metrics.hip, joint_metrics.hip, vis.hip, sample_prep.hip).  They are all one kind of
+// What the streaming kernels share (loss.hip, metrics.hip, joint_metrics.hip, vis.hip, sample_prep.hip, right_view.hip, scene_tiles.hip).  They are all one kind of
 // kernel: BLOCK threads, a capped grid with a grid-stride loop, a lane takes 4 consecutive elements (one wide access where the address
 // allows, scalars otherwise), and a reduction goes thread -> wave (shuffles) -> LDS -> one partial per workgroup in the caller's
 // workspace -> a small finish launch that adds the partials in a fixed order.  No floating-point atomics anywhere: two calls on the
@@ -113,6 +113,19 @@ __device__ __forceinline__ void load4(const long long* p, int nv, long long (&v)
         for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[j] : 0ll;
     }
 }
+// 4 interleaved RGB pixels (12 bytes) at p as three little-endian words: three dword loads, or 3 nv byte loads (the rest zero)
+__device__ __forceinline__ void load_rgb4(const unsigned char* p, int nv, unsigned (&w)[3]) {
+    if (nv == 4 && aligned_to(p, 4)) {
+        const unsigned* q = reinterpret_cast<const unsigned*>(p);
+        w[0] = q[0], w[1] = q[1], w[2] = q[2];
+    } else {
+        w[0] = w[1] = w[2] = 0u;
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+            if (k < 3 * nv) w[k >> 2] |= (unsigned)p[k] << (8 * (k & 3));
+    }
+}
+__device__ __forceinline__ unsigned rgb_byte(const unsigned (&w)[3], int k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
 __device__ __forceinline__ void store4(float* p, int nv, const float (&v)[4]) {
     if (nv == 4 && aligned_to(p, 16)) {
         *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);

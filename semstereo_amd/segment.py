@@ -526,13 +526,15 @@ class PairPipeline:
             self.last_event.record(lane)
         return out
 
-    def join(self, outputs=None, stream=None):
+    def join(self, outputs=None, stream=None, event=None):
         """Make `stream` (default: the current stream) wait for the last issued call and tell the allocator that `outputs` (a
         tensor or any nesting of dicts / lists of tensors: what that call returned) are used there -- the outputs live in the
-        lane's allocator pool, and without record_stream the lane could reuse their memory while the consumer still reads it."""
+        lane's allocator pool, and without record_stream the lane could reuse their memory while the consumer still reads it.
+        `event`: the `last_event` kept from an EARLIER call, to join that call after others were issued behind it."""
         stream = stream or torch.cuda.current_stream()
-        if self.last_event is not None:
-            stream.wait_event(self.last_event)
+        event = self.last_event if event is None else event
+        if event is not None:
+            stream.wait_event(event)
 
         def mark(x):
             if isinstance(x, torch.Tensor):
