@@ -882,6 +882,38 @@ int ss_right_view_fwd(const float* disparity, const void* label, int label_dtype
  * consistent or diff may be NULL, not both.  A negative or NaN threshold, lo >= hi or a NaN range: -1.  2^31 or more elements: -2. */
 int ss_lr_consistency_fwd(const float* disp_left, const float* disp_right, int B, int H, int W, float lo, float hi, float threshold,
                           unsigned char* consistent, float* diff, ss_stream_t stream);
+/* ---- disparity refinement: the left-right check and the semantic hole fill, csrc/disparity_refine.hip ----
+ * The post-processing of a stereo result, with what a generic fill lacks: a hole takes its value from the surface it belongs to.  The
+ * reference has no such step; these are this project's definitions.  Row-wise, per image and row: d the LEFT view's float32 disparity,
+ * dR an optional right-view disparity in the form right_disparity has (-model(right, left) for a model), keep an optional byte mask,
+ * label an optional label map (label_dtype and strides as ss_right_view_fwd reads them), (lo, hi) the valid range.
+ *   in range       lo <= v < hi; a NaN is not
+ *   consistent[x]  ss_lr_consistency_fwd's, by the same device function; defined only with dR
+ *   source[x]      in_range(d[x]) and (no keep or keep[x] != 0) and (no dR or consistent[x])
+ *   class[x]       int(v) where the label value v is integer-valued and 0 <= v < 8; NONE for every other value (negative, 8 or more,
+ *                  a fraction, NaN) and without a label.  US3D's ignored class 5 is an ordinary class here.
+ *   candidates     of a pixel x that is no source, with max_gap >= 1:
+ *                  tier 1, only if class[x] is not NONE: L = the largest x' < x with source[x'] and class[x'] == class[x], R = the
+ *                  smallest such x' > x; each is dropped if |x - x'| > max_gap (the nearest is the only candidate of its side)
+ *                  tier 2, if tier 1 gave no candidate and `fallback` is set: the same without the class condition (sources of class
+ *                  NONE serve it too)
+ *   choice         one side alone wins.  Both, prefer = 0 ("background"): R wins iff d[R] < d[L], or d[R] == d[L] and R - x < x - L --
+ *                  the smaller disparity is the surface further from the sensor; prefer = 1 ("nearest"): R wins iff R - x < x - L, or
+ *                  the distances are equal and d[R] < d[L].  Otherwise L wins.  Plain fp32 comparisons: -0.0 == 0.0.
+ *   out_disparity  d[x] bit for bit on a source, d[x*] of the chosen candidate x* on a filled pixel, fill_value elsewhere
+ *   kind           one byte: 0 kept, 1 filled from the same class, 2 filled from any class, 3 unfilled
+ *   source         int32: x on a kept pixel, x* on a filled one, -1 on an unfilled one
+ *   consistent     one byte 0 / 1
+ * Nothing is interpolated: every output is a selection, one subtraction or a comparison, so the PyTorch composition gives the same
+ * bits.  One workgroup per row: a byte per pixel in LDS, the last / first source column per class carried across the row by an exclusive
+ * integer maximum / minimum scan over the threads; two calls give the same bits.  Any output may be NULL and is then
+ * skipped, at least one is required; consistent needs disparity_right.  lo >= hi or a NaN range, with disparity_right a negative or NaN
+ * threshold, max_gap < 1, prefer or fallback outside {0, 1}, label strides that leave the tensor: -1.  W > 8192 (9 bytes of LDS per
+ * column), 2^31 or more elements, 2^31 or more rows: -2. */
+int ss_disparity_refine_fwd(const float* disparity, const float* disparity_right, const unsigned char* keep, const void* label,
+                            int label_dtype, long long label_row_stride, long long label_image_stride, int B, int H, int W, float lo,
+                            float hi, float threshold, int max_gap, int prefer, int fallback, float fill_value, float* out_disparity,
+                            unsigned char* kind, int* source, unsigned char* consistent, ss_stream_t stream);
 /* ---- scene inference: tile windows and the feathered mosaic, csrc/scene_tiles.hip ----
  * What stands around the model call when the input is a scene and not a tile.  The reference has nothing of the kind (its evaluation
  * loader carries top_pad / right_pad keys that are always 0).

@@ -15,6 +15,7 @@
 // row, 64-bit element offsets.  Nothing here allocates, copies or synchronises, and nothing comes back to the host.
 #include "common.h"
 #include "metrics_decode.h"
+#include "right_view.h"
 #include "stream.h"
 
 namespace {
@@ -23,18 +24,14 @@ using namespace ss::stream;    // BLOCK, grid_for, RowQuad, row_quad, load4, sto
 using ss::metrics::LT_I64;     // label sources: the codes of every label_dtype
 using ss::metrics::LT_U8;
 using ss::metrics::LT_F32;
+using ss::rview::MAX_W;        // owners of a row: 32 KB of LDS
+using ss::rview::lr_diff;      // shared with disparity_refine.hip: right_view.h
+using ss::rview::map_shape;
+using ss::rview::target;
 
 constexpr int GV = 2048;                 // workgroups of a pass
-constexpr int MAX_W = 8192;              // owners of a row: 32 KB of LDS
 
 typedef unsigned char u8;
-
-// the right column a left pixel x with disparity d lands on, or -1
-__device__ __forceinline__ int target(int x, float d, float lo, float hi, int W) {
-    const float t = rintf(ss::sub_rn((float)x, d));
-    const bool lands = (d >= lo) & (d < hi) & (t >= 0.f) & (t < (float)W);       // (NaN fails the first two; -0 passes the third)
-    return lands ? (int)t : -1;
-}
 
 struct ViewArgs {
     const float* disp;         // [B,H,W] contiguous
@@ -123,23 +120,12 @@ __global__ __launch_bounds__(BLOCK) void lr_consistency_k(const float* dl, const
         load4(dl + row + r.x0, r.nv, v);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int t = j < r.nv ? target(r.x0 + j, v[j], lo, hi, W) : -1;
-            e[j] = INFINITY;
-            if (t >= 0) {
-                const float m = dr[row + t];
-                if ((m >= lo) & (m < hi)) e[j] = fabsf(ss::sub_rn(v[j], m));
-            }
+            e[j] = j < r.nv ? lr_diff(r.x0 + j, v[j], dr + row, lo, hi, W) : INFINITY;
             c[j] = e[j] <= threshold ? 1.f : 0.f;
         }
         if (diff) store4(diff + row + r.x0, r.nv, e);
         if (consistent) store4(consistent + row + r.x0, r.nv, c);
     }
-}
-
-// B > 0, H > 0, W > 0 checked by the caller: 0 where the kernels take the shape
-int map_shape(int B, int H, int W) {
-    if ((long long)B * H * W >= (1ll << 31) || (long long)B * H >= (1ll << 31)) return SS_ERR_UNSUPPORTED;
-    return SS_OK;
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// What the streaming kernels share (loss.hip, metrics.hip, joint_metrics.hip, vis.hip, sample_prep.hip, right_view.hip, scene_tiles.hip).  They are all one kind of
+// What the streaming kernels share (loss.hip, metrics.hip, joint_metrics.hip, vis.hip, sample_prep.hip, right_view.hip, disparity_refine.hip, scene_tiles.hip).  They are all one kind of
 // kernel: BLOCK threads, a capped grid with a grid-stride loop, a lane takes 4 consecutive elements (one wide access where the address
 // allows, scalars otherwise), and a reduction goes thread -> wave (shuffles) -> LDS -> one partial per workgroup in the caller's
 // workspace -> a small finish launch that adds the partials in a fixed order.  No floating-point atomics anywhere: two calls on the
@@ -72,6 +72,57 @@ __device__ __forceinline__ void block_minmax(float& lo, float& hi, float* lds) {
     hi = fmaxf(fmaxf(lds[4], lds[5]), fmaxf(lds[6], lds[7]));
 }
 
+// An EXCLUSIVE scan of v[k] over the workgroup's 256 threads, every k, for values that are MONOTONE in the thread: a thread holds
+// `identity` (nothing) or a value that is not below (DOWN: not above) any value an earlier thread holds -- a column of the thread's own
+// chunk of a row, as in disparity_refine.hip.  lds: 16-byte aligned, 4 * K ints with K rounded up to 4.
+//   DOWN = false: thread t receives the MAXIMUM of v[k] over threads 0 .. t - 1, thread 0 `identity`: a prefix, carried left to right
+//   DOWN = true:  thread t receives the MINIMUM of v[k] over threads t + 1 .. 255, thread 255 `identity`: a suffix, carried right to left
+// For monotone values that extreme is the value of the NEAREST thread on that side that holds one, so the scan is a selection.  Order:
+// in a wave one ballot of "holds a value" names that lane (the highest set bit below the lane's own; DOWN: the lowest above) and one
+// shuffle fetches its value -- a doubling scan (steps 1 .. 32) was measured first: its 7 shuffles per value, 126 per thread and row,
+// are LDS-pipe instructions and were most of the kernel's LDS time (profiles/EXPERIMENTS.md, part AC).  The wave's total, its last
+// (first) lane's own value or else what that lane received, goes to lds; the totals of the waves before (after) this one fill in,
+// nearest wave first, where the own wave had nothing.  Selections of integers: no order matters for the bits.  The helper owns the
+// leading barrier, as block_sum does.
+template <int K, bool DOWN>
+__device__ __forceinline__ void block_scan_exclusive(int (&v)[K], int identity, int* lds) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull, above = ~((2ull << lane) - 1ull);      // (lane 63: 2 << 63 is 0, above is 0)
+    int own[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        own[k] = v[k];
+        const unsigned long long side = __ballot(v[k] != identity) & (DOWN ? above : below);
+        const int from = side == 0ull ? lane : (DOWN ? __builtin_ctzll(side) : 63 - __builtin_clzll(side));
+        const int got = __shfl(v[k], from, 64);
+        v[k] = side == 0ull ? identity : got;
+    }
+    constexpr int Q = (K + 3) / 4;                 // a wave's totals as Q 16-byte words
+    int4* totals = reinterpret_cast<int4*>(lds);
+    __syncthreads();
+    if (lane == (DOWN ? 0 : 63)) {
+        int t[4 * Q];
+#pragma unroll
+        for (int k = 0; k < 4 * Q; ++k) t[k] = k >= K ? identity : (own[k < K ? k : 0] != identity ? own[k < K ? k : 0] : v[k < K ? k : 0]);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) totals[wave * Q + q] = make_int4(t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 1; s < 4; ++s) {                  // the waves on that side, nearest first (w is the same for a whole wave)
+        const int w = DOWN ? wave + s : wave - s;
+        if (w < 0 || w >= 4) continue;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const int4 t4 = totals[w * Q + q];
+            const int t[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (4 * q + j < K && v[4 * q + j] == identity) v[4 * q + j] = t[j];
+        }
+    }
+}
+
 // ---------------------------------------------------------------- 4 consecutive elements of a row
 // The 4-pixel groups of all rows of a [B,H,W] map are numbered row by row (QW = ceil(W / 4) per row); the launchers keep their number
 // below 2^31, so the group's row and column come from 32-bit divisions and only the element offsets are 64-bit.
@@ -129,6 +180,15 @@ __device__ __forceinline__ unsigned rgb_byte(const unsigned (&w)[3], int k) { re
 __device__ __forceinline__ void store4(float* p, int nv, const float (&v)[4]) {
     if (nv == 4 && aligned_to(p, 16)) {
         *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < nv) p[j] = v[j];
+    }
+}
+__device__ __forceinline__ void store4(int* p, int nv, const int (&v)[4]) {
+    if (nv == 4 && aligned_to(p, 16)) {
+        *reinterpret_cast<int4*>(p) = make_int4(v[0], v[1], v[2], v[3]);
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j)

@@ -1,0 +1,201 @@
+"""Disparity refinement: the left-right check and a hole fill that takes a hole's value from the surface it belongs to.  The
+post-processing of a stereo result, acting on the mask lr_consistency produces -- with what a generic fill lacks, the predicted class
+of every pixel: roof is filled from roof, ground from ground, and only then from anything.  The reference has no such step.
+
+  fill_disparity     holes of one map (out of range, or masked by `keep`) filled row by row
+  refine_disparity   the left-right check of two estimates, then the same fill of what the check rejects
+
+CUDA tensors run csrc/disparity_refine.hip: one launch, one workgroup per row, nothing waiting on the host.  CPU tensors, other dtypes,
+a label whose rows are not contiguous, rows wider than 8192 and SS_REFINE_HIP=0 take the PyTorch composition below, written without
+boolean indexing and without `.item()`.  modules.PATH_COUNTS["refine_hip"] / ["refine_torch"] count the calls on each path.
+
+The definitions (include/semstereo_hip.h, "disparity refinement", is their one full statement), per image and row:
+  * source[x]: d[x] in range (lo <= d < hi, a NaN is not), and keep[x] if a mask is given, and consistent[x] if a right map is given
+    (data.lr_consistency's definition, the same device function).
+  * class[x]: int(v) for an integer-valued label 0 <= v < 8, none for every other value and without a label.
+  * a pixel that is no source looks left and right for the nearest source of its own class within `max_gap` columns (tier 1), then --
+    with `fallback` -- for the nearest source of any class (tier 2).  One side alone wins; of two, "background" takes the smaller
+    disparity (the surface further from the sensor; equal values: the nearer, then the left), "nearest" the nearer (equal distances:
+    the smaller disparity, then the left).
+  * "disparity": d[x] bit for bit on a source, the chosen candidate's value on a filled pixel, `fill_value` elsewhere; "kind" uint8:
+    0 kept, 1 filled from the same class, 2 filled from any class, 3 unfilled; "source" int32: the column the value came from, -1 on
+    an unfilled pixel; "consistent" bool.
+Nothing is interpolated, so the kernel and the composition agree bit for bit.
+"""
+import numpy as np
+import torch
+
+from . import data as D
+from . import engine as E
+from ._host import _nograd, count
+from ._lib import call, ptr
+
+REFINE_KEYS = ("disparity", "kind", "source", "consistent")
+NUM_CLASSES = 8                              # csrc/disparity_refine.hip: classes 0 .. 7, anything else is "none"
+MAX_WIDTH = 8192                             # ... and 9 bytes of LDS per column
+PREFER = {"background": 0, "nearest": 1}
+_DTYPES = {"disparity": torch.float32, "kind": torch.uint8, "source": torch.int32, "consistent": torch.bool}
+_MAX_ELEMENTS = 2 ** 31
+
+
+def _hip(*tensors):
+    """The kernel takes these tensors: the switch is on and all of them are contiguous CUDA tensors on one device."""
+    if not E.REFINE_HIP:
+        return False
+    dev = tensors[0].device
+    return all(t.is_cuda and t.device == dev and t.is_contiguous() for t in tensors)
+
+
+def _classes(label):
+    """int64 of the label's shape: the class 0 .. 7, or NUM_CLASSES for none."""
+    if label.is_floating_point():
+        inside = (label >= 0) & (label < NUM_CLASSES) & (label == label.trunc())
+        cls = torch.where(inside, label, torch.zeros_like(label)).long()
+    else:
+        cls = label.long()
+        inside = (cls >= 0) & (cls < NUM_CLASSES)
+    return torch.where(inside, cls, torch.full_like(cls, NUM_CLASSES))
+
+
+def _nearest(mask, x, W):
+    """Per pixel the largest column x' < x and the smallest x' > x with mask[x'] (int64 [B,H,W]; -1 and W for none)."""
+    left = torch.where(mask, x, torch.full_like(x, -1)).cummax(2).values
+    right = torch.where(mask, x, torch.full_like(x, W)).flip(2).cummin(2).values.flip(2)
+    none_l, none_r = torch.full_like(left[..., :1], -1), torch.full_like(right[..., :1], W)
+    return torch.cat([none_l, left[..., :-1]], 2), torch.cat([right[..., 1:], none_r], 2)
+
+
+def _choose(d, x, L, R, W, max_gap, prefer):
+    """(a candidate exists, the winning column) of one tier."""
+    has_l, has_r = (L >= 0) & (x - L <= max_gap), (R < W) & (R - x <= max_gap)
+    dl, dr = d.gather(2, L.clamp(min=0)), d.gather(2, R.clamp(max=W - 1))
+    gl, gr = x - L, R - x
+    if prefer == 0:
+        right = (dr < dl) | ((dr == dl) & (gr < gl))
+    else:
+        right = (gr < gl) | ((gr == gl) & (dr < dl))
+    take_r = has_r & (~has_l | right)
+    return has_l | has_r, torch.where(take_r, R, L)
+
+
+def _refine_torch(d, dr, keep, label, lo, hi, threshold, max_gap, prefer, fallback, fill_value, want):
+    B, H, W = d.shape
+    x = torch.arange(W, device=d.device).view(1, 1, W).expand(B, H, W)
+    src = (d >= lo) & (d < hi)
+    if keep is not None:
+        src = src & (keep != 0)
+    out = {}
+    if dr is not None:
+        lands, t, _ = D._targets(d, lo, hi)
+        m = dr.gather(2, t.clamp(max=W - 1))
+        diff = torch.where(lands & (m >= lo) & (m < hi), (d - m).abs(), torch.full_like(d, float("inf")))
+        out["consistent"] = diff <= threshold
+        src = src & out["consistent"]
+    if not {"disparity", "kind", "source"} & set(want):
+        return out
+    has1, s1 = torch.zeros_like(src), torch.full_like(x, -1)
+    if label is not None:
+        cls = _classes(label)
+        L, R = torch.full_like(x, -1), torch.full_like(x, W)
+        for c in range(NUM_CLASSES):                    # per class a cummax / cummin; a pixel takes those of its own class
+            mine = cls == c
+            l, r = _nearest(src & mine, x, W)
+            L, R = torch.where(mine, l, L), torch.where(mine, r, R)
+        has1, s1 = _choose(d, x, L, R, W, max_gap, prefer)
+    filled1 = ~src & has1
+    if fallback:
+        has2, s2 = _choose(d, x, *_nearest(src, x, W), W, max_gap, prefer)
+        filled2 = ~src & ~has1 & has2
+    else:
+        filled2, s2 = torch.zeros_like(src), s1
+    minus = torch.full_like(x, -1)
+    source = torch.where(src, x, torch.where(filled1, s1, torch.where(filled2, s2, minus)))
+    if "source" in want:
+        out["source"] = source.to(torch.int32)
+    if "kind" in want:
+        kind = torch.where(src, 0, torch.where(filled1, 1, torch.where(filled2, 2, 3)))
+        out["kind"] = kind.to(torch.uint8)
+    if "disparity" in want:
+        out["disparity"] = torch.where(source >= 0, d.gather(2, source.clamp(min=0)), torch.full_like(d, fill_value))
+    return out
+
+
+def _refine(disparity, disp_right, label, keep, threshold, maxdisp, disp_range, max_gap, prefer, fallback, fill_value, want, keys):
+    want = tuple(want)
+    if not want or not set(want) <= set(keys):
+        raise ValueError(f"want names some of {keys}, got {want}")
+    if prefer not in PREFER:
+        raise ValueError(f"prefer is one of {tuple(PREFER)}, got {prefer!r}")
+    if (maxdisp is None) == (disp_range is None):
+        raise ValueError("give exactly one of maxdisp (the signed range) and disp_range=(lo, hi)")
+    lo, hi = (-maxdisp, maxdisp) if disp_range is None else disp_range
+    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    if not lo < hi:
+        raise ValueError(f"the disparity range is lo < hi, got ({lo}, {hi})")
+    threshold = float(np.float32(threshold))
+    if disp_right is not None and not threshold >= 0:
+        raise ValueError(f"the threshold is not negative, got {threshold}")
+    if not isinstance(disparity, torch.Tensor) or disparity.dim() not in (2, 3):
+        raise ValueError("maps are [B,H,W] or [H,W]")
+    maps = {"disp_right": disp_right, "label": label, "keep": keep}
+    for name, t in maps.items():
+        if t is not None and (not isinstance(t, torch.Tensor) or t.shape != disparity.shape):
+            raise ValueError(f"{name} has the disparity's shape {tuple(disparity.shape)}, got {None if not isinstance(t, torch.Tensor) else tuple(t.shape)}")
+    squeeze = disparity.dim() == 2
+    if squeeze:
+        disparity = disparity.unsqueeze(0)
+        disp_right, label, keep = (None if t is None else t.unsqueeze(0) for t in (disp_right, label, keep))
+    B, H, W = disparity.shape
+    if max_gap is None:
+        max_gap = W
+    if isinstance(max_gap, bool) or int(max_gap) != max_gap or max_gap < 1:
+        raise ValueError(f"max_gap is an integer >= 1, got {max_gap!r}")
+    max_gap = min(int(max_gap), max(W, 1))
+    fill_value = float(np.float32(fill_value))
+    if keep is not None and keep.dtype == torch.bool:
+        keep = keep.view(torch.uint8) if keep.is_contiguous() else keep.to(torch.uint8)
+    how = None if label is None else D._label_for_kernel(label, disparity)
+    floats = [disparity] + ([disp_right] if disp_right is not None else [])
+    dense = floats + ([keep] if keep is not None else [])
+    if (all(t.dtype == torch.float32 for t in floats) and (keep is None or keep.dtype == torch.uint8) and _hip(*dense)
+            and W <= MAX_WIDTH and 0 < disparity.numel() < _MAX_ELEMENTS and (label is None or how is not None)):
+        count("refine_hip")
+        dev = disparity.device
+        out = {k: torch.empty((B, H, W), dtype=_DTYPES[k], device=dev) for k in want}
+        code, row, img = how if how is not None else (0, W, H * W)
+        with torch.cuda.device(dev):
+            call("ss_disparity_refine_fwd", ptr(disparity), ptr(disp_right), ptr(keep), ptr(label), code, row, img, B, H, W, lo, hi,
+                 threshold, max_gap, PREFER[prefer], int(bool(fallback)), fill_value, *(ptr(out.get(k)) for k in REFINE_KEYS))
+    else:
+        count("refine_torch")
+        out = _refine_torch(disparity.to(torch.float32), None if disp_right is None else disp_right.to(torch.float32), keep, label,
+                            lo, hi, threshold, max_gap, PREFER[prefer], bool(fallback), fill_value, want)
+    out = {k: out[k] for k in want}
+    return {k: v[0] for k, v in out.items()} if squeeze else out
+
+
+@_nograd
+def fill_disparity(disparity, label=None, keep=None, maxdisp=None, disp_range=None, max_gap=None, prefer="background", fallback=True,
+                   fill_value=-999.0, want=("disparity", "kind")):
+    """The holes of a disparity map filled row by row from the surface they belong to (the module's definitions).  `disparity`
+    [B,H,W] (or [H,W]) float32 -- anything else is converted first; `label` of any dtype: the class of every pixel, without it every
+    pixel is of no class and only tier 2 fills; `keep`: a bool / uint8 mask of the pixels that may serve as sources (the `consistent`
+    map of data.lr_consistency, a confidence threshold).  Exactly one of `maxdisp` (-maxdisp <= d < maxdisp) and `disp_range=(lo, hi)`
+    names the values that are sources at all; `max_gap` (default: the row's width) bounds how far a value may travel; `prefer` is
+    "background" or "nearest"; `fallback=False` leaves what the own class cannot fill.  `want` names some of ("disparity", "kind",
+    "source").  Returns a dictionary of tensors on the input's device; nothing waits on the host.  An argument that makes no sense
+    is a ValueError before any launch."""
+    return _refine(disparity, None, label, keep, 0.0, maxdisp, disp_range, max_gap, prefer, fallback, fill_value, want, REFINE_KEYS[:3])
+
+
+@_nograd
+def refine_disparity(disp_left, disp_right, label=None, threshold=1.0, keep=None, maxdisp=None, disp_range=None, max_gap=None,
+                     prefer="background", fallback=True, fill_value=-999.0, want=("disparity", "kind")):
+    """The left-right check and the fill in one pass: a pixel of `disp_left` is a source only if it is also consistent with
+    `disp_right` (data.lr_consistency's definition and arguments: `disp_right[r]` is the disparity of RIGHT pixel r,
+    `-model(right, left)` for a model; `threshold` in pixels), everything else is filled as fill_disparity does.  `want` may also name
+    "consistent", the bool map of the check."""
+    if disp_right is None:
+        raise ValueError("refine_disparity takes two estimates; fill_disparity takes one")
+    return _refine(disp_left, disp_right, label, keep, threshold, maxdisp, disp_range, max_gap, prefer, fallback, fill_value, want,
+                   REFINE_KEYS)

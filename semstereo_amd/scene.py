@@ -35,10 +35,14 @@ import torch.nn as nn
 
 from . import data as D
 from . import engine as E
+from . import refine as R
 from ._host import _const, _nograd, argmax_first, count
 from ._lib import call, ptr
 
 OUTPUTS = ("disparity", "logits", "label", "spread", "count")
+#: what SceneStereo(refine=...) adds: the right view's mosaic (minus the swapped pair's), the check and the filled mosaic
+REFINED_OUTPUTS = ("disparity_right", "consistent", "disparity_refined", "kind")
+_REFINE_ARGS = ("maxdisp", "disp_range", "threshold", "max_gap", "prefer", "fallback", "fill_value")
 _DTYPES = {"label": torch.uint8, "count": torch.uint8}
 MAX_CHANNELS = 8                             # csrc/scene_tiles.hip: logit channels
 MAX_WINDOWS = 256                            # ... and windows per axis
@@ -284,7 +288,7 @@ def blend_tiles(plan, disp_tiles, logit_tiles=None, rows=None, out=None, want=("
 
 # ------------------------------------------------------------------------------------------------ the loop around the model
 class SceneStereo:
-    """`SceneStereo(model, tile=, overlap=, ramp=, lanes=6, batch=1)(left_u8, right_u8, want=("disparity", "label", "spread"))`: the
+    """`SceneStereo(model, tile=, overlap=, ramp=, lanes=6, batch=1, refine=None)(left_u8, right_u8, want=("disparity", "label", "spread"))`: the
     model on a scene pair of any size.  Scenes are uint8 [H,W,3] on the device or on the host (a host scene is copied once, to the
     model's device).  `model` is any callable with the reference's eval convention -- `([disp [B,h,w]], logits [B,C,h,w])`, or
     `[disp]` alone without a segmentation head -- taking the two normalised views [B,3,th,tw].  An nn.Module in eval mode on the
@@ -300,10 +304,23 @@ class SceneStereo:
     that sees it well inside, so overlap_x of about 2 * maxdisp with the default ramp (= the overlap) is the sensible setting; the
     default (256, 256) suits maxdisp = 128.  `spread` shows where the tiles still disagree.
 
-    Not here: a left-right check per scene (data.lr_consistency takes the mosaics of two calls), hole filling, reading GeoTIFFs."""
+    The left-right check per scene: with `refine=dict(maxdisp=, threshold=, max_gap=, prefer=, fallback=)` (refine_disparity's
+    arguments) `want` may also name "disparity_right", "consistent", "disparity_refined" and "kind".  If it does, every tile row is also
+    issued with the views swapped -- the same windows, `model(right_tile, left_tile)` -- and those disparities are blended into a second
+    mosaic band by band alongside the first.  The blend of negated tiles is the exact negation of the blend (products, sums and the
+    division are sign-symmetric), so that mosaic is negated once, in place, after the last band: "disparity_right", the form
+    lr_consistency takes.  One refine_disparity call over the two mosaics and the label mosaic gives the rest; without logits the
+    fill is class-agnostic (tier 2 only).  The swapped tile rows live exactly as long as the others: at most 3 per direction.
 
-    def __init__(self, model, tile=(1024, 1024), overlap=(256, 256), ramp=None, lanes=6, batch=1):
+    Not here: a column pass for rows without any source, reading GeoTIFFs."""
+
+    def __init__(self, model, tile=(1024, 1024), overlap=(256, 256), ramp=None, lanes=6, batch=1, refine=None):
         assert callable(model) and int(lanes) >= 1 and int(batch) >= 1
+        if refine is not None:
+            refine = dict(refine)
+            if not set(refine) <= set(_REFINE_ARGS):
+                raise ValueError(f"refine names some of {_REFINE_ARGS}, got {tuple(refine)}")
+        self.refine = refine
         self.model, self.tile, self.overlap, self.ramp = model, tile, overlap, ramp
         self.lanes, self.batch = int(lanes), int(batch)
         self.pipe, self.plan, self.peak_resident_tile_rows = None, None, 0
@@ -333,13 +350,18 @@ class SceneStereo:
             return result[0][0], result[1]
         return result[0], None
 
-    def _issue(self, r, left, right, piped):
-        """Tile row r through the model: a list of (disp, logits, event) per call, in tile order."""
+    def _issue(self, r, left, right, piped, both=False):
+        """Tile row r through the model: a list of (disp, logits, event) per call, in tile order; with `both` the pair (that list, the
+        same for the swapped views of the same windows)."""
+        views = tile_views(left, right, self.plan.row_origins(r), self.plan.size)
+        calls = self._run(views[0], views[1], piped)
+        return (calls, self._run(views[1], views[0], piped)) if both else calls
+
+    def _run(self, first, second, piped):
         plan = self.plan
-        views = tile_views(left, right, plan.row_origins(r), plan.size)
         calls = []
         for b in range(0, plan.ntx, self.batch):
-            l, rt = views[0][b:b + self.batch], views[1][b:b + self.batch]
+            l, rt = first[b:b + self.batch], second[b:b + self.batch]
             if piped:
                 disp, logits = self._outputs(self.pipe(l, rt))
                 event = self.pipe.last_event
@@ -366,6 +388,29 @@ class SceneStereo:
 
     def __call__(self, left_u8, right_u8, want=("disparity", "label", "spread")):
         want = tuple(want)
+        extra = tuple(k for k in want if k in REFINED_OUTPUTS)
+        if extra:
+            return self._refined(left_u8, right_u8, want, extra)
+        return self._mosaic(left_u8, right_u8, want)
+
+    def _refined(self, left_u8, right_u8, want, extra):
+        """The mosaics of both directions, then one refine_disparity call."""
+        assert self.refine is not None, f"{extra} need SceneStereo(refine=dict(maxdisp=..., ...))"
+        base = tuple(k for k in want if k in OUTPUTS)
+        assert len(base) + len(extra) == len(want), f"want names some of {OUTPUTS + REFINED_OUTPUTS}"
+        out, swapped = self._mosaic(left_u8, right_u8, base + tuple(k for k in ("disparity", "label") if k not in base), both=True)
+        names = {"disparity_refined": "disparity", "kind": "kind", "consistent": "consistent"}
+        asked = tuple(names[k] for k in extra if k in names)
+        if asked:
+            got = R.refine_disparity(out["disparity"], swapped, label=out.get("label"), want=asked, **self.refine)
+            out.update({k: got[names[k]] for k in extra if k in names})
+        out["disparity_right"] = swapped
+        assert all(k in out for k in want), "the model returned no logits: no label mosaic"
+        return {k: out[k] for k in want}
+
+    def _mosaic(self, left_u8, right_u8, want, both=False):
+        """The mosaics named by `want`; with `both` the pair (those, the right view's disparity mosaic from the swapped tiles) and a
+        "label" the model has no logits for is left out, not an error."""
         assert left_u8.dim() == 3 and left_u8.shape[-1] == 3 and right_u8.shape == left_u8.shape, "scenes are uint8 [H,W,3]"
         dev = self._device(left_u8)
         left, right = (v if v.device == dev else v.to(dev, non_blocking=True) for v in (left_u8, right_u8))
@@ -375,9 +420,13 @@ class SceneStereo:
         n, ntx = len(plan), plan.ntx
         disp, logit = [None] * n, [None] * n
         held, out, self.peak_resident_tile_rows = {}, {}, 0
+        back, disp_back, out_back = {}, [None] * n, {}                          # the swapped direction: the same lifetimes
         for r in range(plan.nty + 1):
             if r < plan.nty:
-                held[r] = self._issue(r, left, right, piped)                   # (one tile row ahead of the band that is blended)
+                if both:
+                    held[r], back[r] = self._issue(r, left, right, piped, both=True)
+                else:
+                    held[r] = self._issue(r, left, right, piped)               # (one tile row ahead of the band that is blended)
                 self.peak_resident_tile_rows = max(self.peak_resident_tile_rows, len(held))
             if r == 0:
                 continue
@@ -388,17 +437,29 @@ class SceneStereo:
                 disp[band * ntx:(band + 1) * ntx] = d
                 if lg is not None:
                     logit[band * ntx:(band + 1) * ntx] = lg
+                if both:
+                    disp_back[band * ntx:(band + 1) * ntx] = self._join(back[band])[0]
             has_logits = logit[band * ntx] is not None
+            if both and not has_logits:
+                want = tuple(k for k in want if k != "label")
             assert has_logits or not {"logits", "label"} & set(want), "the model returned no logits: ask for disparity, spread, count"
             if not out:                                                         # (every row is written by its band)
                 C = logit[0].shape[0] if has_logits else 0
                 out = {k: torch.empty((C, H, W) if k == "logits" else (H, W), dtype=_DTYPES.get(k, torch.float32), device=dev) for k in want}
             blend_tiles(plan, disp, logit if has_logits else None, rows=(y0, y1), out=out, want=want)
+            if both:
+                if not out_back:
+                    out_back = {"disparity": torch.empty((H, W), dtype=torch.float32, device=dev)}
+                blend_tiles(plan, disp_back, None, rows=(y0, y1), out=out_back, want=("disparity",))
             for k in [k for k in held if plan.last_use[k] <= band]:             # no later band reads these tile rows
                 del held[k]
                 disp[k * ntx:(k + 1) * ntx] = [None] * ntx
                 logit[k * ntx:(k + 1) * ntx] = [None] * ntx
-        return {k: out[k] for k in want}
+                if both:
+                    del back[k]
+                    disp_back[k * ntx:(k + 1) * ntx] = [None] * ntx
+        out = {k: out[k] for k in want}
+        return (out, out_back["disparity"].neg_()) if both else out
 
     def close(self):
         if self.pipe is not None:
