@@ -1,15 +1,14 @@
 // The classifiers of the model -- nn.Sequential(convbn_3d(32,32,3,1,1), ReLU, Conv3d(32,1,3,p1)): `classif` and `classif_att_`, reference
 // models/SemStereo.py:228-234, called at :278 and :322 -- as ONE pass over the volume: the HEAD form of conv3d_bf16s (see the kernel's
-// header comment in conv3d_bf16s.hip), instantiated in its own translation unit, plus the packing of the head's weights and the
+// header comment in conv3d_bf16s.h), instantiated in its own translation unit, plus the packing of the head's weights and the
 // sum of the tiles' patches.
-#define SS_CONV_GATHER_TU 1
-#include "conv3d_bf16s.hip"
+#include "conv3d_bf16s.h"
 
 namespace {
 
 // matrix row m of the head's A operand -> tap (kd * 9 + kh * 3 + kw), or -1: a lane half of the MFMA's result holds rows
 // m = (r & 3) + 8 * (r >> 2) + 4 * half in register r; register 3 * ps + kh is tap row kh of the (kd, kw) pair ps + 5 * half, so that
-// the sum over kh happens inside a lane (conv3d_bf16s.hip, HEAD)
+// the sum over kh happens inside a lane (conv3d_bf16s.h, HEAD)
 __host__ __device__ inline int head_tap_of_row(int m) {
     const int hf = (m >> 2) & 1, r = (m & 3) + 4 * (m >> 3);
     const int ps = r / 3, kh = r % 3, pair = ps + 5 * hf;
@@ -122,7 +121,7 @@ extern "C" int ss_pack_classifier_head_weights(const float* w2, void* out, ss_st
     return ss::check_launch();
 }
 
-// the one statement of the packed head's size: HEAD_WSLOTS 16-byte fragment slots (conv3d_bf16s.hip stages exactly these)
+// the one statement of the packed head's size: HEAD_WSLOTS 16-byte fragment slots (conv3d_bf16s.h stages exactly these)
 extern "C" int ss_pack_classifier_head_weights_bytes(long long* bytes) {
     SS_REQUIRE(bytes);
     *bytes = HEAD_WSLOTS * 16;

@@ -1,8 +1,7 @@
 // concat_stem with the sparse concat volume formed INSIDE its staging (second half; reference
 // models/SemStereo.py:241-244, 316-320, models/submodule.py:265-288): the GATHER form of conv3d_bf16s, instantiated in its own
-// translation unit so that the two files compile side by side.  See the kernel's header comment in conv3d_bf16s.hip.
-#define SS_CONV_GATHER_TU 1
-#include "conv3d_bf16s.hip"
+// translation unit so that the two files compile side by side.  See the kernel's header comment in conv3d_bf16s.h.
+#include "conv3d_bf16s.h"
 
 extern "C" int ss_conv3d_gather_fwd(const float* right, const float* cand, const float* att, const void* wsplit,
                                     const float* partial, const float* scale, const float* shift, const float* gate, float* out,

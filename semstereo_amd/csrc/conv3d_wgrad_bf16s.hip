@@ -190,9 +190,6 @@ __global__ __launch_bounds__(192, S == 1 ? 3 : 2) void conv3d_wgrad_bf16s(const 
     };
     bool have = advance();
     if (have) { issue_a(); issue_in(nod * S + kd - 1, noh * S + kh - 1, nw0); }
-#ifdef SS_EXP_WG_NOSTAGE
-    bool first_chunk = true;
-#endif
     while (have) {
         const int w0 = nw0;
         // ---- A fragments of this chunk: 2 K-steps x 8 positions of channel l31, split in registers (loaded a chunk ago) ----
@@ -215,22 +212,12 @@ __global__ __launch_bounds__(192, S == 1 ? 3 : 2) void conv3d_wgrad_bf16s(const 
                 af[s][2] = make_uint4(l[0], l[1], l[2], l[3]);
             }
         };
-#ifdef SS_EXP_WG_NOSTAGE          // (timing experiment, wrong results: split + LDS staging only for a wave's first chunk)
-        if (first_chunk)
-#endif
-        {
         if (whole) { split_a(std::true_type{}); store_in(w0, std::true_type{}); }
         else { split_a(std::false_type{}); store_in(w0, std::false_type{}); }
-        }
-#ifdef SS_EXP_WG_NOSTAGE
-        first_chunk = false;
-#endif
         __builtin_amdgcn_wave_barrier();
         // the next chunk's loads fly under this chunk's MFMAs
         have = advance();
-#ifndef SS_EXP_WG_NOLOAD          // (timing experiment, wrong results: no global loads after a wave's first chunk)
         if (have) { issue_a(); issue_in(nod * S + kd - 1, noh * S + kh - 1, nw0); }
-#endif
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             uint4 bfr[3][3];                                // [kw][term]
@@ -261,13 +248,8 @@ __global__ __launch_bounds__(192, S == 1 ? 3 : 2) void conv3d_wgrad_bf16s(const 
             }
             // six cross products per tap, smallest first: (m,m) (h,l) (l,h) (h,m) (m,h) (h,h)
             constexpr int pa[6] = {1, 0, 2, 0, 1, 0}, pb[6] = {1, 2, 0, 1, 0, 0};
-#ifdef SS_EXP_WG_NOMFMA           // (timing experiment, wrong results: one MFMA per tap and K-step instead of six)
-#pragma unroll
-            for (int p = 5; p < 6; ++p)
-#else
 #pragma unroll
             for (int p = 0; p < 6; ++p)
-#endif
 #pragma unroll
                 for (int kw = 0; kw < 3; ++kw)
                     acc[kw] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[s][pa[p]]), __builtin_bit_cast(bf16x8, bfr[kw][pb[p]]),
@@ -441,11 +423,7 @@ __global__ __launch_bounds__(576, 1) void conv3d_wgrad_bf16s_coop(const float* _
 #pragma unroll
     for (int t = 0; t < 3; ++t)
 #pragma unroll
-#ifdef SS_EXP_COOP_NOATOM                                   // (timing-only ablation: wrong results)
-        for (int r = 0; r < 16; ++r) wt[(t * 16 + r) * 64] = acc[t][r];
-#else
         for (int r = 0; r < 16; ++r) unsafeAtomicAdd(wt + (t * 16 + r) * 64, acc[t][r]);
-#endif
 }
 
 // ---- stride 2 with the gout chunk SHARED (r06, last): the per-wave form above is bound by its global loads (271 us as is, 135 without
@@ -467,13 +445,9 @@ __global__ __launch_bounds__(576, 1) void conv3d_wgrad_bf16s_s2a(const float* __
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l31 = lane & 31, half = lane >> 5;
     const int kd = wave / 3, kh = wave - 3 * kd;
-#ifdef SS_S2A_XCD
-    // consecutive chunk ranges (neighbouring depth planes: they read the same input planes) on the SAME XCD, i.e. behind one L2:
-    // workgroups go round-robin over the 8 XCDs, so XCD x takes the contiguous x-th eighth of the ranges
-    const int unit = (gridDim.x % 8 == 0) ? (int)(blockIdx.x % 8) * (int)(gridDim.x / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-#else
+    // (chunk ranges in dispatch order: each XCD on a contiguous eighth of them measured the same, 202.7 / 202.2 vs 202.6 / 201.9 us on
+    // hourglass.conv1's layer -- profiles/EXPERIMENTS.md F.26)
     const int unit = blockIdx.x;
-#endif
     const int c_begin = unit * chunks_per_unit, c_end = min(c_begin + chunks_per_unit, total_chunks);
     const int co0 = (blockIdx.y / ci_tiles) * 32, ci0 = (blockIdx.y % ci_tiles) * 32;
     const int b = blockIdx.z;

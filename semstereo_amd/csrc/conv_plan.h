@@ -11,7 +11,7 @@
 // 2-D layer, and the stride-1 3-D layers that at batch 1 are too small for the 4-row tile -- the deep, narrow layers with the
 // longest K (conv2 / conv4 of the hourglasses: K = 1728 / 3456): there the second accumulator set fits the registers of the 1- and
 // 2-row tiles they run on at small batch; when a larger batch -- or the fill hint of a pipelined call -- moves them onto the 4-row
-// tile, that variant walks the chunk in two passes of two rows (acc_passes of conv3d_bf16s.hip; one pass with a second set for all
+// tile, that variant walks the chunk in two passes of two rows (acc_passes of conv3d_bf16s.h; one pass with a second set for all
 // four rows spilled 15 - 46 registers).  The big 4-row layers (concat_stem, classif.0, hourglass2.conv2) keep the single chain.
 #ifndef SS_ACC_BLOCKED
 #define SS_ACC_BLOCKED 1                  // 0: single chains everywhere (tools/build_variant.sh, for A/B measurements)

@@ -40,20 +40,14 @@ __host__ __device__ constexpr int off_of(int s) {
 constexpr int KST = 27;           // K-steps per 16-channel chunk
 // STREAM (template argument of the kernel): the output goes out with NONTEMPORAL stores (buffer aux 2).  Measured r05 on
 // hourglass2.conv6 (201 MB written, alone): 128 -> 108 us; sc0 + nt the same; nontemporal loads of the skip tensor 119, both 124
-// (profiles/r05_f_deconv_forms.txt).  Which launches stream: ss::plan_deconv3d (conv_plan.h).
-#ifndef SS_DECONV_XCD
-#define SS_DECONV_XCD 0           // 1: every XCD walks a contiguous eighth of the units (see the kernel's last lines)
-#endif
-#ifndef SS_DECONV_SKIP_AUX
-#define SS_DECONV_SKIP_AUX 0      // ... of the skip tensor's loads
-#endif
+// (profiles/r05_f_deconv_forms.txt): the skip tensor's loads keep the plain policy.  Which launches stream: ss::plan_deconv3d (conv_plan.h).
 
 // ---- parity-class groups (r05) ----
 // GRP < 0: a workgroup computes all 8 parity classes of its tile (8 accumulators = 128 registers per wave: two waves per SIMD).
 // GRP = 0 / 1: the classes are split over TWO workgroups per tile -- {0,1,6,7} (15 taps) and {2,3,4,5} (12 taps): each group's
 // output cube I/O is two whole (plane, row) pairs of float2 -- so a wave keeps 4 accumulators, the chunk's weight slab in LDS
 // is the group's taps only (30 / 24 KB instead of 55), and a CU holds three workgroups instead of two; the freed registers
-// also hold the second accumulator set of the chunk-blocked summation (ACCB, see conv3d_bf16s.hip).  Both workgroups stage
+// also hold the second accumulator set of the chunk-blocked summation (ACCB, see conv3d_bf16s.h).  Both workgroups stage
 // the same input tile (it is read twice from L2: 50 MB of the layer's 453 MB), everything else is disjoint.
 struct GrpTable { int ns; int step[KST]; int next_off[KST]; };
 constexpr bool grp_has(int grp, int cls) { return grp < 0 || (grp == 0 ? (cls < 2 || cls >= 6) : (cls >= 2 && cls < 6)); }
@@ -249,9 +243,6 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
     auto skip_phase = [&]() {
-#ifdef SS_EXP_DECONV_NOSKIP           // (timing experiment, wrong results)
-        return;
-#endif
         // ---- 1x1x1 projection of the skip tensor at the 8 output positions of every lane: per 16 skip channels one K-step
         // per parity class; the operand (8 channels x this lane's 2x2x2 cube) comes straight from global memory ----
         const size_t schan = (size_t)Do * out_plane;
@@ -273,7 +264,7 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
                 for (int j = 0; j < 8; ++j) {
                     const int cs = ks * 16 + 8 * half + j;     // channels beyond Cs: a clamped (valid) address, value zeroed
                     v[q][j] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(
-                                                             sres, (int)((lane_s + qo + (unsigned)min(cs, Cs - 1) * schan_b) | dead), 0, SS_DECONV_SKIP_AUX));
+                                                             sres, (int)((lane_s + qo + (unsigned)min(cs, Cs - 1) * schan_b) | dead), 0, 0));
                 }
             }
         };
@@ -418,9 +409,7 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
                 if (NC == 3) lds[(2 * 2 + hf) * C::CS + p] = make_uint4(ll[0], ll[1], ll[2], ll[3]);
             }
         }
-#ifndef SS_EXP_DECONV_NOWAIT      // (timing experiment, wrong results: the upper bound of what a look-ahead of the weight DMA can buy)
         if (F16) __builtin_amdgcn_s_waitcnt(0x0F70);           // vmcnt(0): the LDS-DMA weight loads have landed
-#endif
         __syncthreads();
         const bool more = ck + 1 < nchunks;
         // what the K-steps prefetch: the next chunk of this unit, or (last chunk) the first chunk of the workgroup's next unit
@@ -441,7 +430,7 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
             for (int c = 0; c < NC; ++c) aq[0][c] = lds[WL + c * 64 + lane];
         }
         // ACCB: the chunk's MFMAs accumulate from ZERO in a second register set that joins `acc` once per chunk (two-level
-        // blocked summation, as the CPU GEMMs the reference runs on: conv3d_bf16s.hip has the measurements)
+        // blocked summation, as the CPU GEMMs the reference runs on: conv3d_bf16s.h has the measurements)
         f32x16 tacc[ACCB ? NA : 1];
         if constexpr (ACCB) {
 #pragma unroll
@@ -452,7 +441,7 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             const int s = GP::T.step[k];                       // (compile-time after unrolling)
-            // no vector-memory instruction under a branch (see conv3d_bf16s.hip: the wait-count pass falls back to vmcnt(0)
+            // no vector-memory instruction under a branch (see conv3d_bf16s.h: the wait-count pass falls back to vmcnt(0)
             // at control-flow merges): past the end the last fragment is requested again, the input loads go beyond the buffer
             if (!F16) {
 #pragma unroll
@@ -581,9 +570,6 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
             }
             const float v0 = fmaxf(ss::add_rn(acc[j * 2 + 0][r], sh0), floor_v);
             const float v1 = fmaxf(ss::add_rn(acc[j * 2 + 1][r], sh1), floor_v);
-#ifdef SS_EXP_DECONV_NOSTORE          // (timing experiment: one store per lane instead of 64)
-            if (r == 0 && j == 0)
-#endif
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(ss_u32x2, make_float2(v0, v1)), ores,
                                                   (int)(cok ? vo[j] : 0x80000000u), cb * (int)ochan_b, STREAM ? 2 : 0);
         }
@@ -593,18 +579,9 @@ __global__ __launch_bounds__(256, (SPLIT && !ACCB) ? 3 : 2) void deconv3d_bf16s(
     // unit's stores drain under the next one's loads -- was built and measured in r05: the loop costs 65 spilled registers at the
     // 256 of two workgroups per CU, 129 -> 177 us on hourglass2.conv6, and with the spills equalised persistence itself bought
     // 4 %: profiles/r05_e_deconv_persist.txt.)
-#if SS_DECONV_XCD
-    // XCD-aware unit order (r06): workgroups are dispatched round-robin over the 8 XCDs, so with unit = blockIdx.x a tile and its
-    // neighbours in h (4 indices away) and d never share an L2 and every halo row / plane is fetched from the fabric again (PMC r05:
-    // 537 MB for 453 algorithmic on hourglass2.conv6, the layer that runs at the copy rate of the bytes it moves).  Here XCD k walks
-    // the contiguous k-th eighth of the units: a bijection of [0, nunits) (XCD x gets nunits / 8 units, the first nunits % 8 XCDs one more).
-    const int unit = [&]() {
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3, q = nunits >> 3, r = nunits & 7;
-        return x * q + min(x, r) + j;
-    }();
-#else
+    // Units in dispatch order, round-robin over the 8 XCDs: every XCD walking a contiguous eighth of them instead measured 2-3 % slower
+    // on hourglass2.conv6 (106.7 / 105.5 / 106.4 -> 110.3 / 108.6 / 108.5 us, profiles/r06_r_ab_deconv_xcd.txt).
     const int unit = blockIdx.x;
-#endif
     unit_origin(unit, iw0, ih0, id0);
     if constexpr (!SPLIT) {
         body(std::integral_constant<int, -1>{}, unit);
