@@ -945,6 +945,57 @@ int ss_tile_views_fwd(const unsigned char* left, const unsigned char* right, con
 int ss_tile_blend_fwd(const long long* disp_tiles, const long long* logit_tiles, const int* origin_y, const int* origin_x, int nty,
                       int ntx, int th, int tw, int C, int ry, int rx, int H, int W, int y0, int y1, float* disparity, float* logits,
                       unsigned char* label, float* spread, unsigned char* count, ss_stream_t stream);
+/* ---- training augmentation, csrc/augment.hip ----
+ * The reference's KITTI recipe (datasets/kitti_dataset_15_aug.py:100-156) from the raw arrays on the device, plus a vertical flip and a
+ * horizontal flip with the views swapped.  left, right uint8 [B,H,W,3]; the outputs are th x tw crops.  All photometric steps work on
+ * uint8 values, each stage rounded as PIL rounds it; u is a channel value of the source view that feeds OUTPUT view v of an item:
+ *   luma    (19595 r + 38470 g + 7471 b + 0x8000) >> 16
+ *   blend   blend(deg, x, f) = trunc(clamp(float(deg) + f * float(x - deg), 0, 255)) in fp32, the product rounded before the sum
+ *   T1      brightness then gamma: T1[u] = G[blend(0, u, b)], a 256-entry table per (item, output view) that the CALLER builds
+ *   m       int(S / N + 0.5) in double, S the exact sum of luma(T1[r], T1[g], T1[b]) over the WHOLE source image, N = H W
+ *   u3, u4  u3 = blend(m, T1[u], contrast);  u4[ch] = blend(luma(u3), u3[ch], saturation)
+ *   source  output pixel (y, x) reads row y0 + (vflip ? th - 1 - y : y) and column x0 + x; with the swap the image is mirrored and
+ *           the views exchanged before the crop: column W - 1 - (x0 + x) of the OTHER view, and the maps are right_disparity /
+ *           right_label (ss_right_view_fwd of the full items), mirrored the same way
+ *   occluder  on the output right view of a flagged item: crop pixels inside [cy - sy, cy + sy) x [cx - sx, cx + sx) (rows first,
+ *           clipped to the crop) take floor(Sc / (th tw)) per channel, Sc the exact sum of u4 over the crop of that view
+ *   views   out[b][ch][y][x] = table[ch][u4], table as ss_prep_views_fwd takes it
+ *   maps    the selected pixels: a disparity as float(v) * disp_scale (a swapped item: right_disparity as it is), a label widened to
+ *           float32; level k at (y, x) is the augmented full-resolution map at (y k, x k)
+ * The parameter block, DEVICE memory, little-endian, one record of 560 bytes per item:
+ *   offset  0  int32  y0, x0                     the crop's origin
+ *           8  int32  flags                      bit 0 vflip, bit 1 swap, bit 2 occluder
+ *          12  int32  cy, sy, cx, sx             the occluder in crop coordinates
+ *          28  int32  reserved
+ *          32  float  contrast[2]                per OUTPUT view (0 left, 1 right)
+ *          40  float  saturation[2]
+ *          48  uint8  T1[2][256]
+ * No entry point can read the block: the kernels clamp the origin into [0, H - th] x [0, W - tw] and the rectangle into the crop, so a
+ * wrong block gives wrong pixels, never an address outside the tensors.
+ * Three launches on one stream, in this order: ss_augment_stats_fwd (64-bit integer partial sums of the luma, per workgroup),
+ * ss_augment_occluder_fwd (only when an item has an occluder: integer partial channel sums of u4) and ss_augment_write_fwd, which adds
+ * the partials -- integers, exact in any order: two calls give the same bits -- builds the tables in LDS and writes every non-NULL
+ * output in one pass that reads only the pixels it samples.  No atomics, no finish launch.  Nothing comes back to the host.
+ * NULL or non-positive arguments, th > H, tw > W, a workspace that is too small or not 8-byte aligned: -1.  2^31 or more elements in a
+ * view, more than 65535 items, levels with th or tw not divisible by 16: -2. */
+int ss_augment_param_bytes(int B, long long* bytes);
+int ss_augment_scratch_bytes(int B, int H, int W, int th, int tw, long long* bytes);
+int ss_augment_stats_fwd(const unsigned char* left, const unsigned char* right, const void* params, int B, int H, int W, int th, int tw,
+                         void* workspace, long long workspace_bytes, ss_stream_t stream);
+int ss_augment_occluder_fwd(const unsigned char* left, const unsigned char* right, const void* params, int B, int H, int W, int th,
+                            int tw, void* workspace, long long workspace_bytes, ss_stream_t stream);
+/* have_occluder: 1 when ss_augment_occluder_fwd ran for this block, 0 = the occluder flags are ignored.  disparity (disp_dtype 0 =
+ * float32, 1 = int32) and label (label_dtype and strides as ss_right_view_fwd reads them) may be NULL when none of their outputs is asked
+ * for; right_disparity / right_label float32 [B,H,W] are read for swapped items only and may be NULL when no item swaps (a swapped item
+ * without them gets -999 / 5).  Outputs: out_left, out_right [B,3,th,tw]; disparity_out, label_out [B,th,tw]; disparity_k, label_k
+ * [B,th/k,tw/k].  A NULL output is skipped, at least one is required. */
+int ss_augment_write_fwd(const unsigned char* left, const unsigned char* right, const void* params, const float* table,
+                         const void* disparity, int disp_dtype, float disp_scale, const void* label, int label_dtype,
+                         long long label_row_stride, long long label_image_stride, const float* right_disparity,
+                         const float* right_label, int B, int H, int W, int th, int tw, const void* workspace,
+                         long long workspace_bytes, int have_occluder, float* out_left, float* out_right, float* disparity_out,
+                         float* disparity_4, float* disparity_8, float* disparity_16, float* label_out, float* label_2, float* label_4,
+                         ss_stream_t stream);
 /* Measurement aid (bench.py): a plain device copy, 16 bytes per lane, nontemporal -- the HBM rate a streaming kernel can
  * reach on this box, which SURVEY.md section 8(d) asks the bandwidth fractions to be read against.  bytes % 16 == 0. */
 int ss_tool_copy_fwd(const void* src, void* dst, long long bytes, ss_stream_t stream);

@@ -12,6 +12,8 @@
   data      the datasets' sample preparation on the device (datasets/us3d_.py, datasets/whu_dataset.py): normalised views, ground-truth
             pyramids, gx / gy; right_view (right-view ground truth, the left view's visibility) and lr_consistency;
             RawStereoDataset and DeviceLoader
+  augment   training augmentation on the device: Augmentation (the reference's KITTI recipe, plus a vertical flip and a horizontal flip
+            with the views swapped), AugmentParams, augment_sample; DeviceLoader(..., augment=...)
   refine    what follows the model call: fill_disparity (holes filled from the nearest kept pixel of the same predicted class in the row,
             then of any class) and refine_disparity (the left-right check and that fill in one launch)
   scene     inference on whole scenes of any size: TilePlan (windows, feather weights, bands), tile_views and blend_tiles (the two
@@ -21,7 +23,7 @@
 The compute lives in csrc/libsemstereo_hip.so behind the C ABI of include/semstereo_hip.h.
 Nothing here falls back to the CPU or to the test oracle.
 """
-from . import _lib, data, dist, engine, joint_metrics, losses, metrics, modules, ops, ops_unsigned, refine, scene, segment, train_layers, visualization  # noqa: F401
+from . import _lib, augment, data, dist, engine, joint_metrics, losses, metrics, modules, ops, ops_unsigned, refine, scene, segment, train_layers, visualization  # noqa: F401
 from .install import accelerate, install, install_losses, install_metrics, install_visualization, restore_forward, uninstall  # noqa: F401
 from .losses import LRSC_loss, model_label_loss, model_loss_test, model_loss_train, train_objective  # noqa: F401
 from .metrics import EvalAverager, SegmentationMetric, disparity_metrics, eval_metrics  # noqa: F401
@@ -29,6 +31,7 @@ from .joint_metrics import JointMetric, eval_metrics_joint  # noqa: F401  (the r
 from .visualization import disp_error_image_func, eval_images, feature_vis, label_vis, normalize_image  # noqa: F401
 from .data import DeviceLoader, RawStereoDataset, image_gradients, nearest_pyramid, normalize_views, prepare_sample  # noqa: F401
 from .data import RIGHT_VIEW_KEYS, lr_consistency, right_view  # noqa: F401
+from .augment import AugmentParams, Augmentation, augment_sample  # noqa: F401
 from .refine import REFINE_KEYS, fill_disparity, refine_disparity  # noqa: F401
 from .scene import SceneStereo, TilePlan, blend_tiles, tile_views  # noqa: F401
 from .segment import GraphedSegment, HotSegment, PairPipeline  # noqa: F401

@@ -488,9 +488,12 @@ class DeviceLoader:
     dictionaries on `device`.  On a CUDA device the raw batch is copied from pinned memory on a side stream and prepare_sample runs
     there, one batch ahead of the consumer; a batch is handed to the caller's current stream behind an event, with record_stream on
     every tensor handed out, so `sample['left'].cuda()` in the reference's train_sample is a no-op and the function runs as written.
-    `training`: None = the dataset's own flag; `keys`, `disp_scale`, `maxdisp` and `disp_range` are prepare_sample's."""
+    `training`: None = the dataset's own flag; `keys`, `disp_scale`, `maxdisp` and `disp_range` are prepare_sample's.  `augment`: an
+    augment.Augmentation -- the training branch then draws a batch's parameters on the host and runs augment.augment_sample in place of
+    prepare_sample (crops, so `keys` may not name gx, gy or RIGHT_VIEW_KEYS; without a range of its own the loader hands the swap the
+    Augmentation's maxdisp); the test branch is never augmented."""
 
-    def __init__(self, loader, device=None, keys=None, training=None, disp_scale=None, maxdisp=None, disp_range=None):
+    def __init__(self, loader, device=None, keys=None, training=None, disp_scale=None, maxdisp=None, disp_range=None, augment=None):
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.loader, self.device, self.keys, self.disp_scale = loader, torch.device(device), keys, disp_scale
@@ -498,6 +501,9 @@ class DeviceLoader:
         if training is None:
             training = getattr(getattr(loader, "dataset", None), "training", True)
         self.training = bool(training)
+        self.augment = augment if self.training else None
+        if self.augment is not None and maxdisp is None and disp_range is None:
+            self.range["maxdisp"] = getattr(augment, "maxdisp", None)
         self._stream = None
         if self.device.type == "cuda":
             _const("view_table", self.device, view_table)                        # (on the caller's stream, before the side stream exists)
@@ -512,15 +518,21 @@ class DeviceLoader:
             v = v.pin_memory()
         return v.to(self.device, non_blocking=True)
 
+    def _sample(self, raw):
+        if self.augment is None:
+            return prepare_sample(raw, self.training, self.keys, self.disp_scale, **self.range)
+        from .augment import augment_sample
+        B, H, W, _ = raw["left_u8"].shape
+        return augment_sample(raw, self.augment.draw(B, H, W), self.keys, self.disp_scale, **self.range)
+
     def _prepare(self, raw):
         if self.device.type != "cuda":
-            return prepare_sample(raw, self.training, self.keys, self.disp_scale, **self.range), None
+            return self._sample(raw), None
         if self._stream is None:
             self._stream = torch.cuda.Stream(self.device)
             self._stream.wait_stream(torch.cuda.current_stream(self.device))    # (once: the table's upload is on the caller's stream)
         with torch.cuda.stream(self._stream):
-            sample = prepare_sample({k: self._upload(v) for k, v in raw.items()}, self.training, self.keys, self.disp_scale,
-                                    **self.range)
+            sample = self._sample({k: self._upload(v) for k, v in raw.items()})
             done = torch.cuda.Event()
             done.record(self._stream)
         return sample, done

@@ -724,6 +724,7 @@ VIS_HIP = os.environ.get("SS_VIS_HIP", "1") != "0"      # 0: semstereo_amd.visua
 DATA_HIP = os.environ.get("SS_DATA_HIP", "1") != "0"      # 0: semstereo_amd.data keeps its PyTorch composition (no boolean indexing, no .item()) on the GPU too
 SCENE_HIP = os.environ.get("SS_SCENE_HIP", "1") != "0"      # 0: semstereo_amd.scene keeps its PyTorch composition (no boolean indexing, no .item()) on the GPU too
 REFINE_HIP = os.environ.get("SS_REFINE_HIP", "1") != "0"      # 0: semstereo_amd.refine keeps its PyTorch composition (no boolean indexing, no .item()) on the GPU too
+AUGMENT_HIP = os.environ.get("SS_AUGMENT_HIP", "1") != "0"      # 0: semstereo_amd.augment keeps its PyTorch composition (no boolean indexing, no .item()) on the GPU too
 CLASSIFIER_CL = os.environ.get("SS_CLASSIFIER_CL", "1") != "0"    # 0: plain-layout intermediate inside the classifiers (two generic launches)
 #: the classifiers in ONE pass over the volume (the 32-channel intermediate never leaves the CU: conv3d_classifier.hip) where the
 #: layer is large enough for the 4-row tile at batch 1; SS_CLASSIFIER_FUSED=0: the two-launch forms above
@@ -913,5 +914,5 @@ def deconv3d_bf16s_shift27_hip(x, wsplit, Cout, shift27, relu, nterms, skip, ski
     return out
 
 #: the names tests / tools may SET on this module; `modules.X` forwards reads of them here
-SWITCHES = ("CONV_ENGINE", "DECONV_F16", "DECONV_MIN_WORKGROUPS", "DECONV_BF16S", "CLASSIFIER_CL", "CLASSIFIER_FUSED", "CLASSIFIER_FOLD", "TRAIN_HIP", "SSR_TRAIN_HIP", "HEADS_TRAIN_HIP", "DECODER_TRAIN_HIP", "CONV2D_WGRAD_HIP", "LOSS_HIP", "METRICS_HIP", "JOINT_METRICS_HIP", "VIS_HIP", "DATA_HIP", "SCENE_HIP", "REFINE_HIP", "ATTENTION_FORM", "ATTN_FOLD",
+SWITCHES = ("CONV_ENGINE", "DECONV_F16", "DECONV_MIN_WORKGROUPS", "DECONV_BF16S", "CLASSIFIER_CL", "CLASSIFIER_FUSED", "CLASSIFIER_FOLD", "TRAIN_HIP", "SSR_TRAIN_HIP", "HEADS_TRAIN_HIP", "DECODER_TRAIN_HIP", "CONV2D_WGRAD_HIP", "LOSS_HIP", "METRICS_HIP", "JOINT_METRICS_HIP", "VIS_HIP", "DATA_HIP", "SCENE_HIP", "REFINE_HIP", "AUGMENT_HIP", "ATTENTION_FORM", "ATTN_FOLD",
             "STEM_LEFT_FUSED", "STEM_LEFT_MFMA", "STEM_PRESPLIT", "STEM_GATHER", "STEM_INPLACE", "HEAD_F16", "CONV2D_HIP", "DECODER_HIP", "HEADS_HIP")
