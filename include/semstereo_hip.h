@@ -914,6 +914,36 @@ int ss_disparity_refine_fwd(const float* disparity, const float* disparity_right
                             int label_dtype, long long label_row_stride, long long label_image_stride, int B, int H, int W, float lo,
                             float hi, float threshold, int max_gap, int prefer, int fallback, float fill_value, float* out_disparity,
                             unsigned char* kind, int* source, unsigned char* consistent, ss_stream_t stream);
+/* ---- disparity refinement: class-aware median, csrc/disparity_median.hip ----
+ * What follows the row fill: a 2-D median that removes what a row-wise fill leaves (streaks where neighbouring rows chose different
+ * sources, isolated outliers, rows without any source) and keeps the steps between surfaces sharp, because a pixel is smoothed only
+ * with pixels of its own predicted class.  The reference has no such step; these are this project's definitions.  Per image: d a
+ * float32 disparity map [B,H,W], label an optional label map (label_dtype and strides as ss_right_view_fwd reads them), where an
+ * optional byte mask, (lo, hi) the valid range, r = radius.
+ *   valid(v)       lo <= v < hi; a NaN is not valid
+ *   class          as above: int(v) for an integer-valued label 0 <= v < 8; NONE for every other value and without a label
+ *   window         of (y, x): the pixels (y', x') of the same image with |y - y'| <= r and |x - x'| <= r that lie inside the image.
+ *                  Nothing is padded: border windows are smaller
+ *   members        the valid pixels of the window; with same_class set and class[y,x] != NONE only those whose class equals the
+ *                  centre's.  A centre of class NONE takes all valid pixels.  The centre is a member if it is valid.  n: their number
+ *   order          the total order of the fp32 bit patterns by the monotone integer key k = b ^ ((b >> 31) & 0x7fffffff), b the value's
+ *                  bits as a signed 32-bit integer, compared as signed integers: -0.0 < +0.0, and the result does not depend on how
+ *                  ties are visited.  No member is a NaN, and neither INT32_MIN nor INT32_MAX is the key of a valid value
+ *   pick           the lower median: the member at index (n - 1) / 2 of the ascending order
+ *   target         (where is absent or where[y,x] != 0) and (valid(d[y,x]) or fill_holes) and n >= max(1, min_count)
+ *   out_disparity  the pick, bit for bit, on a target; d[y,x] bit for bit on every other pixel (a NaN or a -999 passes through)
+ *   count          one byte: n on a target, 0 elsewhere
+ * Nothing is interpolated: every output is a selection, so the PyTorch composition gives the same bits.  One workgroup per tile of
+ * 16 x 64 pixels, the tile and its halo as keys in LDS, a fixed compare-exchange network per pixel (non-members enter as alternating
+ * INT32_MIN / INT32_MAX sentinels, so the middle of all (2r + 1)^2 slots is the lower median of the members); two calls give the same
+ * bits.  count may be NULL, out_disparity may not.  A NULL disparity or out_disparity, out_disparity == disparity (neighbours are read
+ * after a pixel could be written: in place is refused), lo >= hi or a NaN range, radius < 1, same_class or fill_holes outside {0, 1},
+ * min_count < 1 or > (2r + 1)^2, a bad label_dtype, label strides that leave the tensor, non-positive B, H or W: -1.  radius > 2,
+ * 2^31 or more elements: -2. */
+int ss_disparity_median_fwd(const float* disparity, const void* label, int label_dtype, long long label_row_stride,
+                            long long label_image_stride, const unsigned char* where, int B, int H, int W, float lo, float hi,
+                            int radius, int same_class, int fill_holes, int min_count, float* out_disparity,
+                            unsigned char* count, ss_stream_t stream);
 /* ---- scene inference: tile windows and the feathered mosaic, csrc/scene_tiles.hip ----
  * What stands around the model call when the input is a scene and not a tile.  The reference has nothing of the kind (its evaluation
  * loader carries top_pad / right_pad keys that are always 0).

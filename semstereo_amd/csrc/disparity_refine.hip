@@ -22,6 +22,7 @@
 // Nothing here allocates, copies or synchronises, and nothing comes back to the host.
 #include "common.h"
 #include "metrics_decode.h"
+#include "refine_class.h"
 #include "right_view.h"
 #include "stream.h"
 
@@ -29,15 +30,15 @@ namespace {
 
 using namespace ss::stream;    // BLOCK, RowQuad, load4, store4, block_scan_exclusive
 using ss::metrics::LT_I64;     // label sources: the codes of every label_dtype
-using ss::metrics::LT_U8;
 using ss::metrics::LT_F32;
+using ss::refine::NCLS;        // classes 0 .. 7; NCLS itself stands for "none" (refine_class.h: class_of, classes4)
+using ss::refine::classes4;
 using ss::rview::MAX_W;
 using ss::rview::lr_diff;
 using ss::rview::map_shape;
 
 constexpr int GV = 2048;                 // workgroups of a pass
-constexpr int NCLS = 8;                  // classes 0 .. 7; NCLS itself stands for "none"
-constexpr int SRC = 16;                  // the source bit of a pixel's byte
+constexpr int SRC = 16;                 // the source bit of a pixel's byte
 constexpr int NOCOL = 0xFFFF;            // no candidate (W <= 8192 < 0xFFFF)
 constexpr int SCRATCH = 48;              // ints of scan scratch: 4 waves x 9 values, each wave's rounded up to 12
 
@@ -58,31 +59,6 @@ struct RefineArgs {
     int B, H, W, chunk;        // chunk: the columns of a thread in steps 2 and 3
     int max_gap, prefer, fallback;
 };
-
-// class[x]: int(v) for an integer-valued 0 <= v < 8, NCLS for every other value (negative, 8 or more, a fraction, NaN)
-__device__ __forceinline__ int class_of(long long v) { return (v < 0 || v >= NCLS) ? NCLS : (int)v; }
-__device__ __forceinline__ int class_of(u8 v) { return v >= NCLS ? NCLS : (int)v; }
-__device__ __forceinline__ int class_of(float f) { return (f >= 0.f && f < (float)NCLS && f == truncf(f)) ? (int)f : NCLS; }
-
-// the classes of 4 consecutive pixels at element offset i of the label map
-__device__ __forceinline__ void classes4(const void* y, int dtype, long long i, int nv, int (&c)[4]) {
-    if (dtype == LT_I64) {
-        long long v[4];
-        load4(reinterpret_cast<const long long*>(y) + i, nv, v);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c[j] = class_of(v[j]);
-    } else if (dtype == LT_U8) {
-        u8 v[4];
-        load4(reinterpret_cast<const u8*>(y) + i, nv, v);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c[j] = class_of(v[j]);
-    } else {
-        float v[4];
-        load4(reinterpret_cast<const float*>(y) + i, nv, v);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c[j] = class_of(v[j]);
-    }
-}
 
 // the candidate of a tier that wins at pixel x: L, R columns or NOCOL; -1 if neither lies within max_gap
 __device__ __forceinline__ int choose(int x, int L, int R, const float* d, int max_gap, int prefer) {

@@ -4,6 +4,7 @@ of every pixel: roof is filled from roof, ground from ground, and only then from
 
   fill_disparity     holes of one map (out of range, or masked by `keep`) filled row by row
   refine_disparity   the left-right check of two estimates, then the same fill of what the check rejects
+  median_disparity   what follows the row fill: a 2-D median in which a pixel is smoothed only with pixels of its own class
 
 CUDA tensors run csrc/disparity_refine.hip: one launch, one workgroup per row, nothing waiting on the host.  CPU tensors, other dtypes,
 a label whose rows are not contiguous, rows wider than 8192 and SS_REFINE_HIP=0 take the PyTorch composition below, written without
@@ -21,6 +22,15 @@ The definitions (include/semstereo_hip.h, "disparity refinement", is their one f
     0 kept, 1 filled from the same class, 2 filled from any class, 3 unfilled; "source" int32: the column the value came from, -1 on
     an unfilled pixel; "consistent" bool.
 Nothing is interpolated, so the kernel and the composition agree bit for bit.
+
+median_disparity (include/semstereo_hip.h, "disparity refinement: class-aware median", is the full statement): per pixel the lower
+median of the valid pixels of its (2r + 1)^2 window that share its class (all valid pixels for a pixel of no class or with
+same_class=False), in the total order of the fp32 bit patterns; border windows are smaller, nothing is padded.  A pixel is replaced
+only if `where` admits it, it is valid itself or fill_holes is set, and the window holds at least min_count members; every other pixel
+passes through bit for bit.  CUDA float32 tensors with radius <= 2 run csrc/disparity_median.hip (a 16 x 64 tile with its halo in
+LDS, a fixed compare-exchange network per pixel), everything else a composition of shifted views and one sort of the integer keys;
+modules.PATH_COUNTS["median_hip"] / ["median_torch"] count the calls.  Not built: the column pass proper (fill_holes reaches
+r x iterations rows, no further), a weighted or bilateral median, sub-pixel blending, radii above 2 on the kernel.
 """
 import numpy as np
 import torch
@@ -36,6 +46,10 @@ MAX_WIDTH = 8192                             # ... and 9 bytes of LDS per column
 PREFER = {"background": 0, "nearest": 1}
 _DTYPES = {"disparity": torch.float32, "kind": torch.uint8, "source": torch.int32, "consistent": torch.bool}
 _MAX_ELEMENTS = 2 ** 31
+MEDIAN_KEYS = ("disparity", "count")
+MEDIAN_TILE = (16, 64)                       # csrc/disparity_median.hip: TH x TW output pixels of a workgroup
+MEDIAN_MAX_RADIUS = 4                        # ... whose networks end at radius 2; 3 and 4 take the composition
+_MEDIAN_KERNEL_RADIUS = 2
 
 
 def _hip(*tensors):
@@ -199,3 +213,113 @@ def refine_disparity(disp_left, disp_right, label=None, threshold=1.0, keep=None
         raise ValueError("refine_disparity takes two estimates; fill_disparity takes one")
     return _refine(disp_left, disp_right, label, keep, threshold, maxdisp, disp_range, max_gap, prefer, fallback, fill_value, want,
                    REFINE_KEYS)
+
+
+def _keys(d):
+    """The monotone integer key of every fp32 bit pattern (int32; the map is its own inverse)."""
+    b = d.view(torch.int32)
+    return b ^ ((b >> 31) & 0x7FFFFFFF)
+
+
+def _median_torch(d, cls, where, lo, hi, r, same_class, fill_holes, min_count, want_count):
+    """One pass of the definitions: (disparity, count or None).  d float32 [B,H,W], cls int64 [B,H,W] (NUM_CLASSES: none), where uint8
+    or None.  The (2r + 1)^2 shifted views of the NaN / none-padded maps, a sort of the members' keys along the stack (a slot that is
+    no member sorts last) and a gather at (n - 1) // 2."""
+    B, H, W = d.shape
+    pad = (r, r, r, r)
+    dp = torch.nn.functional.pad(d, pad, value=float("nan"))
+    cp = torch.nn.functional.pad(cls, pad, value=NUM_CLASSES)
+    vp = (dp >= lo) & (dp < hi)
+    kp = _keys(dp).long()
+    own = (cls != NUM_CLASSES) if same_class else None
+    last = torch.full((), torch.iinfo(torch.int64).max, dtype=torch.int64, device=d.device)
+    slots, n = [], torch.zeros((B, H, W), dtype=torch.int64, device=d.device)
+    for dy in range(2 * r + 1):
+        for dx in range(2 * r + 1):
+            member = vp[:, dy:dy + H, dx:dx + W]
+            if same_class:
+                member = member & (~own | (cp[:, dy:dy + H, dx:dx + W] == cls))
+            slots.append(torch.where(member, kp[:, dy:dy + H, dx:dx + W], last))
+            n = n + member
+    ordered = torch.stack(slots).sort(dim=0).values
+    pick = ordered.gather(0, ((n - 1) // 2).clamp(min=0).unsqueeze(0))[0].to(torch.int32)
+    target = n >= min_count
+    if not fill_holes:
+        target = target & vp[:, r:r + H, r:r + W]
+    if where is not None:
+        target = target & (where != 0)
+    out = torch.where(target, pick ^ ((pick >> 31) & 0x7FFFFFFF), d.view(torch.int32)).view(torch.float32)
+    count = torch.where(target, n, torch.zeros_like(n)).to(torch.uint8) if want_count else None
+    return out, count
+
+
+@_nograd
+def median_disparity(disparity, label=None, where=None, maxdisp=None, disp_range=None, radius=2, same_class=True, fill_holes=False,
+                     min_count=1, iterations=1, want=("disparity",)):
+    """The class-aware 2-D median of a disparity map (the module's definitions), the step after fill_disparity / refine_disparity: it
+    removes the streaks and outliers a row-wise fill leaves without blurring the steps between surfaces.  `disparity` [B,H,W] (or
+    [H,W]) float32 -- anything else is converted first; `label` of any dtype: the class of every pixel, without it (or with
+    `same_class=False`) the median is class-agnostic; `where`: a bool / uint8 mask of the pixels that may change (`kind != 0` of a
+    fill keeps the model's own values bit for bit).  Exactly one of `maxdisp` (-maxdisp <= d < maxdisp) and `disp_range=(lo, hi)`
+    names the valid values; `radius` 1 .. 4 (the kernel takes 1 and 2); `fill_holes` lets a pixel that is not valid take the median
+    of its window; `min_count` members at least, 1 .. (2 radius + 1)^2; `iterations` passes between two buffers -- the caller's
+    tensor is never written.  `want` names some of ("disparity", "count"); "count" uint8 is the number of members of the last pass
+    on a replaced pixel, 0 elsewhere.  Returns a dictionary of tensors on the input's device; nothing waits on the host.  An
+    argument that makes no sense is a ValueError before any launch."""
+    want = tuple(want)
+    if not want or not set(want) <= set(MEDIAN_KEYS):
+        raise ValueError(f"want names some of {MEDIAN_KEYS}, got {want}")
+    if (maxdisp is None) == (disp_range is None):
+        raise ValueError("give exactly one of maxdisp (the signed range) and disp_range=(lo, hi)")
+    lo, hi = (-maxdisp, maxdisp) if disp_range is None else disp_range
+    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    if not lo < hi:
+        raise ValueError(f"the disparity range is lo < hi, got ({lo}, {hi})")
+    for name, v, least, most in (("radius", radius, 1, MEDIAN_MAX_RADIUS), ("iterations", iterations, 1, None)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least or (most is not None and v > most):
+            raise ValueError(f"{name} is an integer {least} .. {'' if most is None else most}, got {v!r}")
+    radius, iterations = int(radius), int(iterations)
+    window = (2 * radius + 1) ** 2
+    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or not 1 <= min_count <= window:
+        raise ValueError(f"min_count is an integer 1 .. {window} at radius {radius}, got {min_count!r}")
+    if not isinstance(disparity, torch.Tensor) or disparity.dim() not in (2, 3):
+        raise ValueError("maps are [B,H,W] or [H,W]")
+    for name, t in (("label", label), ("where", where)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.shape != disparity.shape):
+            raise ValueError(f"{name} has the disparity's shape {tuple(disparity.shape)}, got {None if not isinstance(t, torch.Tensor) else tuple(t.shape)}")
+    same_class, fill_holes, min_count = bool(same_class), bool(fill_holes), int(min_count)
+    squeeze = disparity.dim() == 2
+    if squeeze:
+        disparity = disparity.unsqueeze(0)
+        label, where = (None if t is None else t.unsqueeze(0) for t in (label, where))
+    B, H, W = disparity.shape
+    if where is not None and where.dtype == torch.bool:
+        where = where.view(torch.uint8) if where.is_contiguous() else where.to(torch.uint8)
+    how = None if label is None else D._label_for_kernel(label, disparity)
+    dense = [disparity] + ([where] if where is not None else [])
+    if (disparity.dtype == torch.float32 and (where is None or where.dtype == torch.uint8) and _hip(*dense)
+            and radius <= _MEDIAN_KERNEL_RADIUS and 0 < disparity.numel() < _MAX_ELEMENTS and (label is None or how is not None)):
+        count("median_hip")
+        dev = disparity.device
+        code, row, img = how if how is not None else (0, W, H * W)
+        src, counts = disparity, None
+        with torch.cuda.device(dev):
+            bufs = [torch.empty((B, H, W), dtype=torch.float32, device=dev) for _ in range(min(iterations, 2))]
+            for i in range(iterations):
+                dst = bufs[i % 2]
+                if "count" in want and i == iterations - 1:
+                    counts = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+                call("ss_disparity_median_fwd", ptr(src), ptr(label), code, row, img, ptr(where), B, H, W, lo, hi, radius,
+                     int(same_class), int(fill_holes), min_count, ptr(dst), ptr(counts))
+                src = dst
+        out = {"disparity": src, "count": counts}
+    else:
+        count("median_torch")
+        src, counts = disparity.to(torch.float32), None
+        cls = torch.full((B, H, W), NUM_CLASSES, dtype=torch.int64, device=disparity.device) if label is None else _classes(label)
+        for i in range(iterations):
+            src, counts = _median_torch(src.contiguous(), cls, where, lo, hi, radius, same_class, fill_holes, min_count,
+                                        "count" in want and i == iterations - 1)
+        out = {"disparity": src, "count": counts}
+    out = {k: out[k] for k in want}
+    return {k: v[0] for k, v in out.items()} if squeeze else out

@@ -41,8 +41,10 @@ from ._lib import call, ptr
 
 OUTPUTS = ("disparity", "logits", "label", "spread", "count")
 #: what SceneStereo(refine=...) adds: the right view's mosaic (minus the swapped pair's), the check and the filled mosaic
-REFINED_OUTPUTS = ("disparity_right", "consistent", "disparity_refined", "kind")
-_REFINE_ARGS = ("maxdisp", "disp_range", "threshold", "max_gap", "prefer", "fallback", "fill_value")
+REFINED_OUTPUTS = ("disparity_right", "consistent", "disparity_refined", "kind", "disparity_median")
+_REFINE_ARGS = ("maxdisp", "disp_range", "threshold", "max_gap", "prefer", "fallback", "fill_value", "median")
+#: refine=dict(..., median=dict(...)): median_disparity's arguments, and which pixels may change ("filled": kind != 0; "all")
+_MEDIAN_ARGS = ("radius", "iterations", "where", "same_class", "fill_holes", "min_count")
 _DTYPES = {"label": torch.uint8, "count": torch.uint8}
 MAX_CHANNELS = 8                             # csrc/scene_tiles.hip: logit channels
 MAX_WINDOWS = 256                            # ... and windows per axis
@@ -312,7 +314,13 @@ class SceneStereo:
     lr_consistency takes.  One refine_disparity call over the two mosaics and the label mosaic gives the rest; without logits the
     fill is class-agnostic (tier 2 only).  The swapped tile rows live exactly as long as the others: at most 3 per direction.
 
-    Not here: a column pass for rows without any source, reading GeoTIFFs."""
+    The median after the fill: with `refine=dict(..., median=dict(radius=2, iterations=1, where="filled", fill_holes=True, ...))`
+    (median_disparity's arguments) `want` may also name "disparity_median": one median_disparity call over "disparity_refined" and
+    the label mosaic, with the refine arguments' range, follows the refine_disparity call.  where="filled" (the default) lets only
+    the pixels the fill touched or left unfilled change (`kind != 0`), so the model's kept values stay bit for bit; where="all"
+    gives no mask.  A call that does not name "disparity_median" makes no further launch.
+
+    Not here: a column pass proper for rows without any source (fill_holes reaches radius x iterations rows), reading GeoTIFFs."""
 
     def __init__(self, model, tile=(1024, 1024), overlap=(256, 256), ramp=None, lanes=6, batch=1, refine=None):
         assert callable(model) and int(lanes) >= 1 and int(batch) >= 1
@@ -320,7 +328,12 @@ class SceneStereo:
             refine = dict(refine)
             if not set(refine) <= set(_REFINE_ARGS):
                 raise ValueError(f"refine names some of {_REFINE_ARGS}, got {tuple(refine)}")
-        self.refine = refine
+            median = refine.pop("median", None)
+            if median is not None:
+                median = dict(median)
+                if not set(median) <= set(_MEDIAN_ARGS) or median.setdefault("where", "filled") not in ("filled", "all"):
+                    raise ValueError(f'median names some of {_MEDIAN_ARGS} with where "filled" or "all", got {median}')
+        self.refine, self.median = refine, (median if refine is not None else None)
         self.model, self.tile, self.overlap, self.ramp = model, tile, overlap, ramp
         self.lanes, self.batch = int(lanes), int(batch)
         self.pipe, self.plan, self.peak_resident_tile_rows = None, None, 0
@@ -401,9 +414,19 @@ class SceneStereo:
         out, swapped = self._mosaic(left_u8, right_u8, base + tuple(k for k in ("disparity", "label") if k not in base), both=True)
         names = {"disparity_refined": "disparity", "kind": "kind", "consistent": "consistent"}
         asked = tuple(names[k] for k in extra if k in names)
+        median = None
+        if "disparity_median" in extra:
+            assert self.median is not None, "disparity_median needs SceneStereo(refine=dict(..., median=dict(...)))"
+            median = dict(self.median)
+            masked = median.pop("where") == "filled"
+            asked += tuple(k for k in (("disparity", "kind") if masked else ("disparity",)) if k not in asked)
         if asked:
             got = R.refine_disparity(out["disparity"], swapped, label=out.get("label"), want=asked, **self.refine)
             out.update({k: got[names[k]] for k in extra if k in names})
+        if median is not None:
+            valid = {k: self.refine[k] for k in ("maxdisp", "disp_range") if k in self.refine}
+            out["disparity_median"] = R.median_disparity(got["disparity"], label=out.get("label"), where=(got["kind"] != 0) if masked else None,
+                                                         **valid, **median)["disparity"]
         out["disparity_right"] = swapped
         assert all(k in out for k in want), "the model returned no logits: no label mosaic"
         return {k: out[k] for k in want}
