@@ -330,7 +330,10 @@ def softmax_regression(logits, maxdisp, want_prob=False, _range=None):
 def upsample_softmax_regression(coarse, maxdisp, H, W, _range=None):
     """Fused models/SemStereo.py:279-285: trilinear 2x up-sampling of the classifier output `coarse` [B,1,maxdisp,H/2,W/2]
     to [B,1,2*maxdisp,H,W], softmax over the disparity axis, its expectation and variance -- one kernel.
-    -> (att_weights [B,1,2m,H,W], disp [B,H,W], var [B,1,H,W]).  Inference only; needs exact 2x and 2*maxdisp <= 128."""
+    -> (att_weights [B,1,2m,H,W], disp [B,H,W], var [B,1,H,W]).  `_range` = (dmin, D): plane p is disparity dmin + p (signed:
+    (-m, 2m); unsigned: (0, m)).  Needs exact 2x in every dimension and D <= 128 planes (signed maxdisp/4 <= 64, unsigned
+    maxdisp/4 <= 128).  This call records no autograd graph; under autograd the same kernel runs as
+    train._UpsampleSoftmaxRegression with its backward kernels."""
     coarse = _c(coarse)
     dev = _lib.require_device(coarse)
     B = coarse.shape[0]
@@ -563,13 +566,17 @@ def sample_strength(left, right, pred0, var, gamma, beta):
     return out
 
 
-#: the fused selection keeps a pixel's probabilities in registers: D = 2 * (maxdisp // 4) <= 128 (attention_tail.hip)
+#: the fused selection keeps a pixel's probabilities in registers or LDS: D <= 128 planes (attention_tail.hip) -- D = 2 * (maxdisp // 4)
+#: on the signed range (maxdisp <= 256), D = maxdisp // 4 on the unsigned one (maxdisp <= 512)
 TOPK_CANDIDATES_MAX_D = 128
 
 
 def topk_candidates(att_weights, strength, maxdisp, k, _range=None):
     """Fused models/SemStereo.py:295-310: att_weights [B,1,2m,H,W] (up-sampled logits), strength [B,5,H,W]
-    -> (att_topk [B,1,k,H,W], disparity_sample_topk [B,k,H,W], pred_att [B,H,W]).  Inference only."""
+    -> (att_topk [B,1,k,H,W], disparity_sample_topk [B,k,H,W], pred_att [B,H,W]).  `_range` = (dmin, D): the candidate of
+    plane p is dmin + p (signed: (-m, 2m); unsigned: (0, m)); k <= D <= TOPK_CANDIDATES_MAX_D.  Ties in probability go to the
+    lower plane (a stable descending sort).  This call records no autograd graph; under autograd the same kernel runs as
+    train._TopkCandidates with its backward kernel."""
     att_weights, strength = _c(att_weights), _c(strength)
     dev = _lib.require_device(att_weights, strength)
     B, one, D, H, W = att_weights.shape

@@ -162,7 +162,7 @@ SEGMENT_WHU = {
 }
 _SEGMENT_SEED = {"whu128_md128": 828, "whu96x160_md256_b2": 832, "s128": 800, "s96x160_b2": 804, "s256_md128": 808, "s192x256_md192": 812,
                  "s256_md128_cal": 816, "f1024_md128_cal": 820, "f2048_md192_cal": 824, "f1024_md128_cal_b": 836, "f1024_md128_cal_c": 840,
-                 "f1024_md128": 844, "t256_md64": 872}
+                 "f1024_md128": 844, "t256_md64": 872, "whu_t128_md128": 908}
 
 # "_cal": BatchNorm running statistics CALIBRATED on the fixture's own input (one pass of the reference with batch
 # statistics, momentum 1), as a trained network has them: every layer's activations are normalised, so the costs of a
@@ -201,7 +201,11 @@ DELTA2 = 1e-4
 # tools/pick_train_seed.py: at this size the median relative gradient difference of ANY fp32 evaluation of the graph sits at 0.7 - 7e-4
 # (exact-fp32 engine: 1.1e-4 ... 6.7e-4 over the seeds tried; f16x3 0.75e-4 ... 5e-4) and most seeds put one ReLU of the matching branch
 # on the other side of zero (a few parameters at 1e-2); seed 872 has neither: median 7.5e-5, worst 1.4e-3 on the default engine
-SEGMENT_TRAIN = {"t256_md64": (1, 256, 256, 64)}
+# `whu_t128_md128`: one training step of the UNSIGNED segment (models/SemStereo_WHU.py; tests/test_tail_ranges_gpu.py), D4 = 32.  Of ten
+# seeds scanned with the float64 oracle in training mode, 908 keeps the top-24 cut furthest from a tie: the smallest relative gap between
+# the 24th and 25th probabilities is 6.9e-5 (the fixture seed 828 of `whu128_md128`: 1.02e-5, on DELTA24_REL itself);
+# tests/test_tail_range_cases.py asserts the margin
+SEGMENT_TRAIN = {"t256_md64": (1, 256, 256, 64), "whu_t128_md128": (1, 128, 128, 128)}
 
 
 def segment_shape(name):
