@@ -10,6 +10,12 @@
 
 namespace {
 
+// The normalised value before the residual and the ReLU: (x - mean) * sc + bias, sc = invstd * weight.  The difference is formed first:
+// with the mean folded into a shift (fmaf(x, sc, bias - mean * sc)) the shift's own rounding, 2^-24 * |mean| * sc, came on top of the
+// fp32 mean's -- twice the error of fp32 PyTorch at a mean of 1000 std, and +-0.016 instead of the bias on a constant channel of 1000.1.
+// The forward and the backward's mask from x both call this, so they decide every element alike.
+__device__ __forceinline__ float bn_pre(float x, float mu, float sc, float b) { return fmaf(x - mu, sc, b); }
+
 // ---- per-channel reductions over [B, C, N] (N = D*H*W) -----------------------------------------------------------------------
 // block (chunk, c): sums of a slice of the channel's B*N elements; 256 threads x float4; totals in double through atomics
 // sums[c*NS + k]; MODE 0: (x, x^2)   MODE 1: (g', g' * xhat) with g' = g * (y > 0 if relu), xhat = (x - mean) * invstd
@@ -27,10 +33,14 @@ __global__ __launch_bounds__(256) void channel_reduce_kernel(const float* __rest
     const long long base = ((long long)b * C + c) * N;
     const long long i0 = (long long)blockIdx.x * per_block, i1 = min(i0 + per_block, N);
     float s0 = 0.f, s1 = 0.f;
+    // MODE 0 sums x and x^2 in double from the first add: the variance is E[x^2] - mean^2, and an fp32 square alone (2^-24 of x^2) is
+    // 2^-24 * (mean / std)^2 of the variance -- 4e-5 of invstd at a mean of 100 std, 0.06 of absolute variance on a constant channel of
+    // 1000.1.  The pass stays HBM-bound: one conversion, one add and one fma in fp64 per four bytes read
+    double q0 = 0.0, q1 = 0.0;
     const float mu = (MODE == 1) ? mean[c] : 0.f, is = (MODE == 1) ? invstd[c] : 0.f;
-    // (r06) y == NULL with relu: the ReLU mask from x itself -- the forward's own fmaf(x, sc, sh) > 0 -- instead of a third tensor read
+    // (r06) y == NULL with relu: the ReLU mask from x itself -- the forward's own bn_pre(x) > 0 -- instead of a third tensor read
     const bool remask = MODE == 1 && relu && y == nullptr;
-    const float msc = remask ? is * (w ? w[c] : 1.f) : 0.f, msh = remask ? fmaf(-mu, msc, bias ? bias[c] : 0.f) : 0.f;
+    const float msc = remask ? is * (w ? w[c] : 1.f) : 0.f, msh = (remask && bias) ? bias[c] : 0.f;
     // (r06) 16 bytes per lane where the channel rows allow it (N % 4 == 0; per_block is then a multiple of 4): the scalar loop ran at
     // ~2 TB/s of traffic, 4.4 ms of the 1024^2 training step in the four BatchNorm passes
     const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | (MODE == 1 ? reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) : 0);   // (NULL y: no bits)
@@ -40,14 +50,14 @@ __global__ __launch_bounds__(256) void channel_reduce_kernel(const float* __rest
             const float ae[4] = {av.x, av.y, av.z, av.w};
             if (MODE == 0) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { s0 += ae[e]; s1 += ae[e] * ae[e]; }
+                for (int e = 0; e < 4; ++e) { const double v = ae[e]; q0 += v; q1 = fma(v, v, q1); }
             } else if (MODE == 1) {
                 const float4 xv = *reinterpret_cast<const float4*>(x + base + i);
                 const float xe[4] = {xv.x, xv.y, xv.z, xv.w};
                 float ye[4] = {1.f, 1.f, 1.f, 1.f};
                 if (remask) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) ye[e] = fmaf(xe[e], msc, msh);
+                    for (int e = 0; e < 4; ++e) ye[e] = bn_pre(xe[e], mu, msc, msh);
                 } else if (relu) {
                     const float4 yv = *reinterpret_cast<const float4*>(y + base + i);
                     ye[0] = yv.x; ye[1] = yv.y; ye[2] = yv.z; ye[3] = yv.w;
@@ -65,18 +75,18 @@ __global__ __launch_bounds__(256) void channel_reduce_kernel(const float* __rest
     } else
     for (long long i = i0 + threadIdx.x; i < i1; i += 256) {
         if (MODE == 0) {
-            const float v = a[base + i];
-            s0 += v; s1 += v * v;
+            const double v = a[base + i];
+            q0 += v; q1 = fma(v, v, q1);
         } else if (MODE == 1) {
             float g = a[base + i];
-            if (relu && !((remask ? fmaf(x[base + i], msc, msh) : y[base + i]) > 0.f)) g = 0.f;
+            if (relu && !((remask ? bn_pre(x[base + i], mu, msc, msh) : y[base + i]) > 0.f)) g = 0.f;
             s0 += g; s1 += g * ((x[base + i] - mu) * is);
         } else {
             s0 += a[base + i];
         }
     }
     __shared__ double red[2][4];
-    double d0 = s0, d1 = s1;
+    double d0 = (MODE == 0) ? q0 : (double)s0, d1 = (MODE == 0) ? q1 : (double)s1;
     for (int o = 32; o > 0; o >>= 1) {
         d0 += __shfl_xor(d0, o);
         d1 += __shfl_xor(d1, o);
@@ -118,8 +128,8 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int c = (int)((i / N) % C);
-    const float sc = invstd[c] * (w ? w[c] : 1.f), sh = fmaf(-mean[c], sc, bias ? bias[c] : 0.f);
-    float v = fmaf(x[i], sc, sh);             // (the backward recomputes this very expression for the ReLU mask when it is not given y)
+    const float sc = invstd[c] * (w ? w[c] : 1.f);
+    float v = bn_pre(x[i], mean[c], sc, bias ? bias[c] : 0.f);     // (the backward recomputes this very expression for the ReLU mask when it is not given y)
     if (res) v += res[i];
     if (relu) v = fmaxf(v, 0.f);
     y[i] = v;
@@ -132,10 +142,10 @@ __global__ __launch_bounds__(256) void bn_apply_v4_kernel(const float* __restric
                                                            float* __restrict__ y, int C, long long N, int relu) {
     const int c = blockIdx.y;
     const long long base = ((long long)blockIdx.z * C + c) * N;
-    const float sc = invstd[c] * (w ? w[c] : 1.f), sh = fmaf(-mean[c], sc, bias ? bias[c] : 0.f);
+    const float mu = mean[c], sc = invstd[c] * (w ? w[c] : 1.f), sh = bias ? bias[c] : 0.f;
     for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i < N; i += (long long)gridDim.x * 1024) {
         const float4 xv = *reinterpret_cast<const float4*>(x + base + i);
-        float v[4] = {fmaf(xv.x, sc, sh), fmaf(xv.y, sc, sh), fmaf(xv.z, sc, sh), fmaf(xv.w, sc, sh)};
+        float v[4] = {bn_pre(xv.x, mu, sc, sh), bn_pre(xv.y, mu, sc, sh), bn_pre(xv.z, mu, sc, sh), bn_pre(xv.w, mu, sc, sh)};
         if (res) {
             const float4 rv = *reinterpret_cast<const float4*>(res + base + i);
             v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;
@@ -158,7 +168,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_v4_kernel(const float* __res
     const long long base = ((long long)blockIdx.z * C + c) * N;
     const float mu = mean[c], is = invstd[c], ws = (w ? w[c] : 1.f) * is;
     const bool remask = relu && y == nullptr;                // (the mask from x: see channel_reduce_kernel)
-    const float msh = fmaf(-mu, ws, bias ? bias[c] : 0.f);
+    const float msh = bias ? bias[c] : 0.f;
     const float mg = (float)(sums[2 * c] / count), mgx = (float)(sums[2 * c + 1] / count);
     if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) {      // the parameter gradients as floats (r06: two strided copies per layer)
         if (gb) gb[c] = (float)sums[2 * c];
@@ -172,7 +182,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_v4_kernel(const float* __res
         if (remask) {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                if (!(fmaf(xe[e], ws, msh) > 0.f)) gv[e] = 0.f;
+                if (!(bn_pre(xe[e], mu, ws, msh) > 0.f)) gv[e] = 0.f;
         } else if (relu) {
             const float4 yq = *reinterpret_cast<const float4*>(y + base + i);
             const float ye[4] = {yq.x, yq.y, yq.z, yq.w};
@@ -209,7 +219,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     float gv = g[i];
     if (relu) {
         const float sc = invstd[c] * (w ? w[c] : 1.f);
-        const float pre = (y != nullptr) ? y[i] : fmaf(x[i], sc, fmaf(-mean[c], sc, bias ? bias[c] : 0.f));
+        const float pre = (y != nullptr) ? y[i] : bn_pre(x[i], mean[c], sc, bias ? bias[c] : 0.f);
         if (!(pre > 0.f)) gv = 0.f;
     }
     if (dres) dres[i] = gv;                   // the residual's gradient: the incoming one behind the ReLU mask
@@ -547,8 +557,8 @@ extern "C" int ss_batchnorm_eval_bwd(const float* grad_y, const float* x, const 
 
 // Both backward forms with the parameter gradients ALSO as floats: grad_weight / grad_bias [C] (either may be NULL) beside the doubles in
 // `work`; grad_residual may be NULL; batch_statistics = 1: the backward of ss_batchnorm_train_fwd / _res_fwd, 0: of ss_batchnorm_eval_fwd.
-// y may be NULL where the forward had a ReLU and NO residual: the mask is then recomputed from x -- fmaf(x, invstd * w, bias - mean *
-// invstd * w) > 0, the forward's own expression, with `bias` the forward's (NULL = none) -- and two of the backward's seven tensor
+// y may be NULL where the forward had a ReLU and NO residual: the mask is then recomputed from x -- fmaf(x - mean, invstd * w, bias)
+// > 0, the forward's own expression (bn_pre), with `bias` the forward's (NULL = none) -- and two of the backward's seven tensor
 // passes (y in the statistics pass and in the apply pass) are not read
 extern "C" int ss_batchnorm_bwd_pg(const float* grad_y, const float* x, const float* y, const float* mean, const float* invstd,
                                    const float* weight, const float* bias, float* grad_x, float* grad_residual, double* work,
