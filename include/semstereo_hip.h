@@ -944,6 +944,41 @@ int ss_disparity_median_fwd(const float* disparity, const void* label, int label
                             long long label_image_stride, const unsigned char* where, int B, int H, int W, float lo, float hi,
                             int radius, int same_class, int fill_holes, int min_count, float* out_disparity,
                             unsigned char* count, ss_stream_t stream);
+/* ---- disparity refinement: speckle removal, csrc/disparity_speckle.hip ----
+ * What comes before the row fill: small connected blobs of wrong disparity (a mismatched roof patch, a tree crown, a moving car) pass
+ * the left-right check, would serve the fill as sources and are larger than half a median window.  They are found by connected-
+ * component labelling and removed.  The reference has no such step and OpenCV's filterSpeckles knows no classes; these are this
+ * project's definitions.  Per image: d a float32 disparity map [B,H,W], label an optional label map (label_dtype and strides as
+ * ss_right_view_fwd reads them), where an optional byte mask, (lo, hi) the valid range, max_diff a float32 >= 0, max_size an
+ * integer >= 0.
+ *   valid(v)       lo <= v < hi; a NaN is not valid (the median's definition)
+ *   class          as above: int(v) for an integer-valued label 0 <= v < 8; NONE for every other value and without a label
+ *   link(p, q)     of two 4-neighbours (left / right, up / down) of the same image: both are valid, and
+ *                  fabsf(d[p] - d[q]) <= max_diff with ONE fp32 subtraction, rounded once (a NaN difference links nothing), and --
+ *                  with same_class set -- class[p] == class[q], NONE being equal to NONE.  Diagonals never link; nothing links
+ *                  across the images of a batch
+ *   component      the relation is symmetric; a component is a class of its transitive closure: a chain 0, 1, 2, 3 ... with
+ *                  max_diff = 1 is ONE component, as in OpenCV
+ *   component[p]   int32: the smallest linear index y * W + x among the pixels of p's component; -1 on a pixel that is not valid
+ *   size[p]        int32: the number of pixels of p's component; 0 on a pixel that is not valid
+ *   speckle[p]     one byte 0 / 1: valid(d[p]) and size[p] <= max_size and (where is absent or where[p] != 0)
+ *   out_disparity  fill_value on a speckle; d[p] bit for bit on every other pixel (a NaN or a -999 passes through)
+ * component and size are integers fixed by these definitions, whatever order the unions ran in: the kernel, the PyTorch composition
+ * and a sequential flood fill agree exactly, and two calls give the same bits.  Union-find with the smallest index as the root, four
+ * launches on the caller's stream: one workgroup per tile of 32 x 64 pixels labels its tile in LDS; one thread per linked pixel pair
+ * across a tile boundary unites the two in global memory (agent-scope integer atomicMin, every decision on the value it returned);
+ * every tile-local root adds its count to its final root (integer atomicAdd: one per local root, not one per pixel); one pass per
+ * pixel writes the outputs.  No launch waits on another workgroup, no floating-point atomics, nothing comes back to the host.
+ * scratch: ss_disparity_speckle_scratch(B, H, W) bytes (two int32 planes), 16-byte aligned, wholly overwritten by every call.
+ * Each output may be NULL and is then skipped, at least one is required.  The last pass reads nothing of the disparity but d[p] for
+ * p: out_disparity == disparity (in place) is ALLOWED.  A NULL disparity or scratch, all outputs NULL, lo >= hi or a NaN range, a
+ * negative or NaN max_diff, max_size < 0, same_class outside {0, 1}, a bad label_dtype, label strides that leave the tensor,
+ * non-positive B, H or W, a scratch that is too small or not 16-byte aligned: -1.  2^31 or more elements: -2. */
+int ss_disparity_speckle_scratch(int B, int H, int W, long long* bytes);
+int ss_disparity_speckle_fwd(const float* disparity, const void* label, int label_dtype, long long label_row_stride,
+                             long long label_image_stride, const unsigned char* where, int B, int H, int W, float lo, float hi,
+                             float max_diff, int max_size, int same_class, float fill_value, void* scratch, long long scratch_bytes,
+                             float* out_disparity, unsigned char* out_speckle, int* out_size, int* out_component, ss_stream_t stream);
 /* ---- scene inference: tile windows and the feathered mosaic, csrc/scene_tiles.hip ----
  * What stands around the model call when the input is a scene and not a tile.  The reference has nothing of the kind (its evaluation
  * loader carries top_pad / right_pad keys that are always 0).

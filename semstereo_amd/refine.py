@@ -5,6 +5,7 @@ of every pixel: roof is filled from roof, ground from ground, and only then from
   fill_disparity     holes of one map (out of range, or masked by `keep`) filled row by row
   refine_disparity   the left-right check of two estimates, then the same fill of what the check rejects
   median_disparity   what follows the row fill: a 2-D median in which a pixel is smoothed only with pixels of its own class
+  filter_speckles    what comes before it: small connected blobs of one class and one disparity level found and removed
 
 CUDA tensors run csrc/disparity_refine.hip: one launch, one workgroup per row, nothing waiting on the host.  CPU tensors, other dtypes,
 a label whose rows are not contiguous, rows wider than 8192 and SS_REFINE_HIP=0 take the PyTorch composition below, written without
@@ -31,6 +32,19 @@ passes through bit for bit.  CUDA float32 tensors with radius <= 2 run csrc/disp
 LDS, a fixed compare-exchange network per pixel), everything else a composition of shifted views and one sort of the integer keys;
 modules.PATH_COUNTS["median_hip"] / ["median_torch"] count the calls.  Not built: the column pass proper (fill_holes reaches
 r x iterations rows, no further), a weighted or bilateral median, sub-pixel blending, radii above 2 on the kernel.
+
+filter_speckles (include/semstereo_hip.h, "disparity refinement: speckle removal", is the full statement): two 4-neighbours of an
+image link if both are valid, their disparities differ by at most max_diff (one fp32 subtraction) and -- with same_class -- they are
+of one class (none equals none); a component is a class of the transitive closure, so a ramp 0, 1, 2, ... with max_diff = 1 is one
+component.  "component" int32 is the smallest index y * W + x of a pixel's component (-1 on a pixel that is not valid), "size" int32
+the number of its pixels (0), "speckle" bool: valid, size <= max_size, and admitted by `where`; "disparity" is fill_value on a speckle
+and d bit for bit elsewhere.  All of it is integers fixed by the definitions: CUDA float32 tensors run csrc/disparity_speckle.hip
+(union-find in LDS per 32 x 64 tile, the links across tile edges united by integer atomicMin in global memory, the tiles' counts
+added up on the final roots, one pass for the outputs: four launches, nothing waiting on the host), everything else a composition
+that propagates the smallest index over the four link masks with pointer jumping -- and asks the host once per round whether
+anything changed: the one place in this module where the composition waits.  modules.PATH_COUNTS["speckle_hip"] /
+["speckle_torch"] count the calls.  Not built: 8-connectivity, a max_diff that grows with the disparity, statistics of a component
+other than its size.
 """
 import numpy as np
 import torch
@@ -38,7 +52,7 @@ import torch
 from . import data as D
 from . import engine as E
 from ._host import _nograd, count
-from ._lib import call, ptr
+from ._lib import call, ptr, query_bytes
 
 REFINE_KEYS = ("disparity", "kind", "source", "consistent")
 NUM_CLASSES = 8                              # csrc/disparity_refine.hip: classes 0 .. 7, anything else is "none"
@@ -50,6 +64,9 @@ MEDIAN_KEYS = ("disparity", "count")
 MEDIAN_TILE = (16, 64)                       # csrc/disparity_median.hip: TH x TW output pixels of a workgroup
 MEDIAN_MAX_RADIUS = 4                        # ... whose networks end at radius 2; 3 and 4 take the composition
 _MEDIAN_KERNEL_RADIUS = 2
+SPECKLE_KEYS = ("disparity", "speckle", "size", "component")
+SPECKLE_TILE = (32, 64)                      # csrc/disparity_speckle.hip: TH x TW pixels of a workgroup's union-find in LDS
+_SPECKLE_DTYPES = {"disparity": torch.float32, "speckle": torch.bool, "size": torch.int32, "component": torch.int32}
 
 
 def _hip(*tensors):
@@ -321,5 +338,121 @@ def median_disparity(disparity, label=None, where=None, maxdisp=None, disp_range
             src, counts = _median_torch(src.contiguous(), cls, where, lo, hi, radius, same_class, fill_holes, min_count,
                                         "count" in want and i == iterations - 1)
         out = {"disparity": src, "count": counts}
+    out = {k: out[k] for k in want}
+    return {k: v[0] for k, v in out.items()} if squeeze else out
+
+
+def _speckle_torch(d, cls, where, lo, hi, max_diff, max_size, same_class, fill_value, want):
+    """The definitions by label propagation: d float32 [B,H,W], cls int64 [B,H,W] (NUM_CLASSES: none), where uint8 or None.  Every
+    valid pixel starts with its own index; a round takes the minimum over the linked 4-neighbours and then follows the labels as
+    pointers (label[p] = label[label[p]], three times); the rounds end when one changes nothing, which the host is asked once per
+    round.  At that point a label is constant over a component, never above any of its pixels' indices and always one of them: the
+    smallest."""
+    B, H, W = d.shape
+    HW = H * W
+    dev = d.device
+    valid = (d >= lo) & (d < hi)
+
+    def link(a, b):
+        m = valid[a] & valid[b] & ((d[a] - d[b]).abs() <= max_diff)
+        return m & (cls[a] == cls[b]) if same_class else m
+    every = slice(None)
+    right = link((every, every, slice(0, W - 1)), (every, every, slice(1, W)))            # p links p + 1
+    down = link((every, slice(0, H - 1), every), (every, slice(1, H), every))             # p links p + W
+    no_col, no_row = torch.zeros((B, H, 1), dtype=torch.bool, device=dev), torch.zeros((B, 1, W), dtype=torch.bool, device=dev)
+    to_r, to_l = torch.cat([right, no_col], 2), torch.cat([no_col, right], 2)
+    to_d, to_u = torch.cat([down, no_row], 1), torch.cat([no_row, down], 1)
+    none = torch.full((), HW, dtype=torch.int64, device=dev)                               # the label of a pixel that is not valid
+    col, row = none.expand(B, H, 1), none.expand(B, 1, W)
+    lab = torch.where(valid, torch.arange(HW, device=dev).view(1, H, W).expand(B, H, W), none)
+    while True:
+        new = torch.minimum(lab, torch.where(to_r, torch.cat([lab[:, :, 1:], col], 2), none))
+        new = torch.minimum(new, torch.where(to_l, torch.cat([col, lab[:, :, :-1]], 2), none))
+        new = torch.minimum(new, torch.where(to_d, torch.cat([lab[:, 1:], row], 1), none))
+        new = torch.minimum(new, torch.where(to_u, torch.cat([row, lab[:, :-1]], 1), none)).reshape(B, HW)
+        for _ in range(3):
+            new = torch.cat([new, none.expand(B, 1)], 1).gather(1, new)                   # (slot HW: none points at none)
+        new = new.view(B, H, W)
+        if bool(torch.equal(new, lab)):                                                    # the host waits here, once per round
+            break
+        lab = new
+    flat = lab.reshape(B, HW)
+    out = {}
+    if {"disparity", "speckle", "size"} & set(want):
+        ones = valid.reshape(B, HW).to(torch.int64)
+        size = torch.zeros((B, HW + 1), dtype=torch.int64, device=dev).scatter_add_(1, flat, ones).gather(1, flat).view(B, H, W)
+        size = torch.where(valid, size, torch.zeros_like(size))
+        speckle = valid & (size <= max_size)
+        if where is not None:
+            speckle = speckle & (where != 0)
+        out["size"], out["speckle"] = size.to(torch.int32), speckle
+        if "disparity" in want:
+            out["disparity"] = torch.where(speckle, torch.full_like(d, fill_value), d)
+    if "component" in want:
+        out["component"] = torch.where(valid, lab, torch.full_like(lab, -1)).to(torch.int32)
+    return out
+
+
+@_nograd
+def filter_speckles(disparity, label=None, where=None, maxdisp=None, disp_range=None, max_size=100, max_diff=1.0, same_class=True,
+                    fill_value=-999.0, want=("disparity", "speckle")):
+    """Small connected blobs of a disparity map removed (the module's definitions), the step before fill_disparity /
+    refine_disparity: a blob that passed the left-right check would be a source of the fill and be smeared along its rows; marked as
+    a speckle (`keep=~speckle`) it is filled from its surroundings instead.  `disparity` [B,H,W] (or [H,W]) float32 -- anything else
+    is converted first; `label` of any dtype: the class of every pixel -- a roof blob is not linked to the ground it touches; without
+    it (or with `same_class=False`) only the disparities decide; `where`: a bool / uint8 mask of the pixels that may be removed.
+    Exactly one of `maxdisp` (-maxdisp <= d < maxdisp) and `disp_range=(lo, hi)` names the valid values; `max_diff` >= 0: the
+    largest step between two linked neighbours; `max_size` >= 0: the largest component that is removed (0: none is).  `want` names
+    some of ("disparity", "speckle", "size", "component"); an output that is not named is not allocated, and the caller's tensor is
+    never written.  Returns a dictionary of tensors on the input's device.  On the kernel nothing waits on the host; the PyTorch
+    composition (CPU tensors, other dtypes, a label whose rows are not contiguous, SS_REFINE_HIP=0) asks the host once per round of
+    its label propagation whether anything changed.  An argument that makes no sense is a ValueError before any launch."""
+    want = tuple(want)
+    if not want or not set(want) <= set(SPECKLE_KEYS):
+        raise ValueError(f"want names some of {SPECKLE_KEYS}, got {want}")
+    if (maxdisp is None) == (disp_range is None):
+        raise ValueError("give exactly one of maxdisp (the signed range) and disp_range=(lo, hi)")
+    lo, hi = (-maxdisp, maxdisp) if disp_range is None else disp_range
+    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    if not lo < hi:
+        raise ValueError(f"the disparity range is lo < hi, got ({lo}, {hi})")
+    if isinstance(max_size, bool) or not isinstance(max_size, (int, np.integer)) or not 0 <= max_size < _MAX_ELEMENTS:
+        raise ValueError(f"max_size is an integer 0 .. 2^31 - 1, got {max_size!r}")
+    if isinstance(max_diff, bool) or not isinstance(max_diff, (int, float, np.integer, np.floating)) or not max_diff >= 0:
+        raise ValueError(f"max_diff is a number >= 0, got {max_diff!r}")
+    max_size, max_diff, same_class = int(max_size), float(np.float32(max_diff)), bool(same_class)
+    if not isinstance(disparity, torch.Tensor) or disparity.dim() not in (2, 3):
+        raise ValueError("maps are [B,H,W] or [H,W]")
+    for name, t in (("label", label), ("where", where)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.shape != disparity.shape):
+            raise ValueError(f"{name} has the disparity's shape {tuple(disparity.shape)}, got {None if not isinstance(t, torch.Tensor) else tuple(t.shape)}")
+    fill_value = float(np.float32(fill_value))
+    squeeze = disparity.dim() == 2
+    if squeeze:
+        disparity = disparity.unsqueeze(0)
+        label, where = (None if t is None else t.unsqueeze(0) for t in (label, where))
+    B, H, W = disparity.shape
+    if where is not None and where.dtype == torch.bool:
+        where = where.view(torch.uint8) if where.is_contiguous() else where.to(torch.uint8)
+    how = None if label is None else D._label_for_kernel(label, disparity)
+    dense = [disparity] + ([where] if where is not None else [])
+    if (disparity.dtype == torch.float32 and (where is None or where.dtype == torch.uint8) and _hip(*dense)
+            and 0 < disparity.numel() < _MAX_ELEMENTS and (label is None or how is not None)):
+        count("speckle_hip")
+        dev = disparity.device
+        code, row, img = how if how is not None else (0, W, H * W)
+        nbytes = query_bytes("ss_disparity_speckle_scratch", B, H, W)
+        with torch.cuda.device(dev):
+            scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            out = {k: torch.empty((B, H, W), dtype=_SPECKLE_DTYPES[k], device=dev) for k in want}
+            call("ss_disparity_speckle_fwd", ptr(disparity), ptr(label), code, row, img, ptr(where), B, H, W, lo, hi, max_diff, max_size,
+                 int(same_class), fill_value, ptr(scratch), nbytes, *(ptr(out.get(k)) for k in SPECKLE_KEYS))
+    elif disparity.numel() == 0:
+        count("speckle_torch")
+        out = {k: torch.empty((B, H, W), dtype=_SPECKLE_DTYPES[k], device=disparity.device) for k in want}
+    else:
+        count("speckle_torch")
+        cls = torch.full((B, H, W), NUM_CLASSES, dtype=torch.int64, device=disparity.device) if label is None else _classes(label)
+        out = _speckle_torch(disparity.to(torch.float32), cls, where, lo, hi, max_diff, max_size, same_class, fill_value, want)
     out = {k: out[k] for k in want}
     return {k: v[0] for k, v in out.items()} if squeeze else out

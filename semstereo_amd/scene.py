@@ -41,8 +41,10 @@ from ._lib import call, ptr
 
 OUTPUTS = ("disparity", "logits", "label", "spread", "count")
 #: what SceneStereo(refine=...) adds: the right view's mosaic (minus the swapped pair's), the check and the filled mosaic
-REFINED_OUTPUTS = ("disparity_right", "consistent", "disparity_refined", "kind", "disparity_median")
-_REFINE_ARGS = ("maxdisp", "disp_range", "threshold", "max_gap", "prefer", "fallback", "fill_value", "median")
+REFINED_OUTPUTS = ("disparity_right", "consistent", "disparity_refined", "kind", "disparity_median", "speckle")
+_REFINE_ARGS = ("maxdisp", "disp_range", "threshold", "max_gap", "prefer", "fallback", "fill_value", "median", "speckle")
+#: refine=dict(..., speckle=dict(...)): filter_speckles' arguments
+_SPECKLE_ARGS = ("max_size", "max_diff", "same_class")
 #: refine=dict(..., median=dict(...)): median_disparity's arguments, and which pixels may change ("filled": kind != 0; "all")
 _MEDIAN_ARGS = ("radius", "iterations", "where", "same_class", "fill_holes", "min_count")
 _DTYPES = {"label": torch.uint8, "count": torch.uint8}
@@ -320,6 +322,12 @@ class SceneStereo:
     the pixels the fill touched or left unfilled change (`kind != 0`), so the model's kept values stay bit for bit; where="all"
     gives no mask.  A call that does not name "disparity_median" makes no further launch.
 
+    Speckles before the fill: with `refine=dict(..., speckle=dict(max_size=, max_diff=, same_class=))` (filter_speckles' arguments)
+    one filter_speckles call over the left mosaic and the label mosaic, with the refine arguments' range, comes before the
+    refine_disparity call, which gets `keep=~speckle`: a small blob that passes the left-right check is then no source, its pixels
+    have `kind != 0` and take their surroundings' value.  `want` may also name "speckle", the bool map.  Without the `speckle` key no
+    such call is made and every output keeps its bits.
+
     Not here: a column pass proper for rows without any source (fill_holes reaches radius x iterations rows), reading GeoTIFFs."""
 
     def __init__(self, model, tile=(1024, 1024), overlap=(256, 256), ramp=None, lanes=6, batch=1, refine=None):
@@ -333,7 +341,13 @@ class SceneStereo:
                 median = dict(median)
                 if not set(median) <= set(_MEDIAN_ARGS) or median.setdefault("where", "filled") not in ("filled", "all"):
                     raise ValueError(f'median names some of {_MEDIAN_ARGS} with where "filled" or "all", got {median}')
+            speckle = refine.pop("speckle", None)
+            if speckle is not None:
+                speckle = dict(speckle)
+                if not set(speckle) <= set(_SPECKLE_ARGS):
+                    raise ValueError(f"speckle names some of {_SPECKLE_ARGS}, got {tuple(speckle)}")
         self.refine, self.median = refine, (median if refine is not None else None)
+        self.speckle = speckle if refine is not None else None
         self.model, self.tile, self.overlap, self.ramp = model, tile, overlap, ramp
         self.lanes, self.batch = int(lanes), int(batch)
         self.pipe, self.plan, self.peak_resident_tile_rows = None, None, 0
@@ -420,11 +434,16 @@ class SceneStereo:
             median = dict(self.median)
             masked = median.pop("where") == "filled"
             asked += tuple(k for k in (("disparity", "kind") if masked else ("disparity",)) if k not in asked)
+        valid = {k: self.refine[k] for k in ("maxdisp", "disp_range") if k in self.refine}
+        keep = None
+        if "speckle" in extra or (self.speckle is not None and {"disparity", "kind"} & set(asked)):       # (the check itself knows no keep)
+            assert self.speckle is not None, "speckle needs SceneStereo(refine=dict(..., speckle=dict(...)))"
+            out["speckle"] = R.filter_speckles(out["disparity"], label=out.get("label"), want=("speckle",), **valid, **self.speckle)["speckle"]
+            keep = ~out["speckle"]
         if asked:
-            got = R.refine_disparity(out["disparity"], swapped, label=out.get("label"), want=asked, **self.refine)
+            got = R.refine_disparity(out["disparity"], swapped, label=out.get("label"), keep=keep, want=asked, **self.refine)
             out.update({k: got[names[k]] for k in extra if k in names})
         if median is not None:
-            valid = {k: self.refine[k] for k in ("maxdisp", "disp_range") if k in self.refine}
             out["disparity_median"] = R.median_disparity(got["disparity"], label=out.get("label"), where=(got["kind"] != 0) if masked else None,
                                                          **valid, **median)["disparity"]
         out["disparity_right"] = swapped
