@@ -914,6 +914,43 @@ int ss_disparity_refine_fwd(const float* disparity, const float* disparity_right
                             int label_dtype, long long label_row_stride, long long label_image_stride, int B, int H, int W, float lo,
                             float hi, float threshold, int max_gap, int prefer, int fallback, float fill_value, float* out_disparity,
                             unsigned char* kind, int* source, unsigned char* consistent, ss_stream_t stream);
+/* ---- disparity refinement: fill along rows and columns, csrc/disparity_fill2d.hip ----
+ * The same fill looking in four directions, as SGM and MC-CNN fill occlusions: a hole whose own surface continues directly above or
+ * below it need not be filled from max_gap columns away, or from another class, and a row without any source is no longer lost.  `in
+ * range`, `consistent`, `source`, `class`, the tiers, `kind` and `out_disparity` are those of the section "disparity refinement",
+ * unchanged.  What changes, per image, with max_gap_x >= 1 and max_gap_y >= 1:
+ *   candidates     of a pixel (y, x) that is no source.  Tier 1, only if class[y,x] is not NONE: L / R = the nearest source of its
+ *                  class in its ROW to the left / right, exactly as above; U / D = the nearest source of its class in its COLUMN above
+ *                  (y' < y) / below (y' > y).  L, R are dropped if |x - x'| > max_gap_x; U, D if |y - y'| > max_gap_y.  Tier 2, if
+ *                  tier 1 gave no candidate and `fallback` is set: the same without the class condition
+ *   choice         the candidates in the order L, R, U, D, each with its value v = d at the candidate and its distance g (columns or
+ *                  rows).  prefer = 0 ("background") takes the least (v, g, order), prefer = 1 ("nearest") the least (g, v, order):
+ *                  tuples compared lexicographically, v by plain fp32 comparisons (-0.0 == 0.0; no source is a NaN).  With only L
+ *                  and R present this is the row fill's rule word for word: R wins iff d[R] < d[L], or the values are equal and R is
+ *                  nearer ("nearest": iff R is nearer, or equally far and smaller), otherwise L
+ *   out_disparity  d[y,x] bit for bit on a source, d at the chosen candidate (y*, x*) on a filled pixel, fill_value elsewhere
+ *   kind           one byte: 0 kept, 1 filled from the same class, 2 filled from any class, 3 unfilled
+ *   source         int32: the column x* of the chosen pixel; x on a kept pixel, -1 on an unfilled one
+ *   source_row     int32: its row y*; y on a kept pixel, -1 on an unfilled one
+ *   consistent     one byte 0 / 1, as above
+ * Nothing is interpolated: every output is a selection or a comparison, so the kernels, the PyTorch composition and a sequential
+ * restatement agree bit for bit, and two calls give the same bits.  Four launches on the caller's stream over tiles of 64 rows x 256
+ * columns: the byte of every pixel and per tile and column the last / first source row of every class; an exclusive scan of those
+ * summaries over the at most 128 tiles of a column; a sweep down and up every tile that writes each pixel's U and D as 16-bit rows
+ * (0xFFFF for none); and one workgroup per row that runs the row fill's own scans and makes the choice.  No launch waits on another
+ * workgroup, no atomics, nothing comes back to the host.
+ * scratch: ss_disparity_fill2d_scratch(B, H, W) bytes, 16-byte aligned; every byte that is read is written by the same call first.
+ * Each output may be NULL and is then skipped, at least one is required; consistent needs disparity_right.  A NULL disparity or
+ * scratch, all outputs NULL, consistent without disparity_right, lo >= hi or a NaN range, with disparity_right a negative or NaN
+ * threshold, a gap < 1, prefer or fallback outside {0, 1}, a bad label_dtype, label strides that leave the tensor, non-positive B, H
+ * or W, a scratch that is too small or not 16-byte aligned: -1.  W > 8192 or H > 8192 (rows and columns travel as 16-bit values),
+ * 2^31 or more elements: -2.  All of it is checked before any launch. */
+int ss_disparity_fill2d_scratch(int B, int H, int W, long long* bytes);
+int ss_disparity_fill2d_fwd(const float* disparity, const float* disparity_right, const unsigned char* keep, const void* label,
+                            int label_dtype, long long label_row_stride, long long label_image_stride, int B, int H, int W, float lo,
+                            float hi, float threshold, int max_gap_x, int max_gap_y, int prefer, int fallback, float fill_value,
+                            void* scratch, long long scratch_bytes, float* out_disparity, unsigned char* kind, int* source,
+                            int* source_row, unsigned char* consistent, ss_stream_t stream);
 /* ---- disparity refinement: class-aware median, csrc/disparity_median.hip ----
  * What follows the row fill: a 2-D median that removes what a row-wise fill leaves (streaks where neighbouring rows chose different
  * sources, isolated outliers, rows without any source) and keeps the steps between surfaces sharp, because a pixel is smoothed only

@@ -15,7 +15,7 @@
   augment   training augmentation on the device: Augmentation (the reference's KITTI recipe, plus a vertical flip and a horizontal flip
             with the views swapped), AugmentParams, augment_sample; DeviceLoader(..., augment=...)
   refine    what follows the model call: fill_disparity (holes filled from the nearest kept pixel of the same predicted class in the row,
-            then of any class), refine_disparity (the left-right check and that fill in one launch), median_disparity (a 2-D
+            then of any class; axes="both": in the row and the column), refine_disparity (the left-right check and that fill), median_disparity (a 2-D
             median in which a pixel is smoothed only with pixels of its own class) and filter_speckles (small connected blobs
             of one class removed before the fill)
   scene     inference on whole scenes of any size: TilePlan (windows, feather weights, bands), tile_views and blend_tiles (the two
@@ -34,7 +34,7 @@ from .visualization import disp_error_image_func, eval_images, feature_vis, labe
 from .data import DeviceLoader, RawStereoDataset, image_gradients, nearest_pyramid, normalize_views, prepare_sample  # noqa: F401
 from .data import RIGHT_VIEW_KEYS, lr_consistency, right_view  # noqa: F401
 from .augment import AugmentParams, Augmentation, augment_sample  # noqa: F401
-from .refine import MEDIAN_KEYS, REFINE_KEYS, SPECKLE_KEYS, fill_disparity, filter_speckles, median_disparity, refine_disparity  # noqa: F401
+from .refine import MEDIAN_KEYS, REFINE_KEYS, REFINE_KEYS_2D, SPECKLE_KEYS, fill_disparity, filter_speckles, median_disparity, refine_disparity  # noqa: F401
 from .scene import SceneStereo, TilePlan, blend_tiles, tile_views  # noqa: F401
 from .segment import GraphedSegment, HotSegment, PairPipeline  # noqa: F401
 

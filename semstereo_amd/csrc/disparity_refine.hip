@@ -8,7 +8,8 @@
 // chunk = ceil(W / BLOCK) rounded up to 4 and Wp = chunk * BLOCK >= W columns:
 //   1. a coalesced row-quad pass computes source and class of every pixel (the right map's value is a scalar gather) and packs them
 //      into one byte per pixel: bits 0-3 the class, 8 for none; bit 4 source.  Columns W .. Wp - 1 are "none, no source".
-//   2. thread t owns columns [t * chunk, (t + 1) * chunk).  It reduces them to the last source column per class and of any class
+//   2. (steps 2 and 3 are refine_rows_steps.inc and the choice is refine_rows.h's: disparity_fill2d.hip runs the same text)
+//      thread t owns columns [t * chunk, (t + 1) * chunk).  It reduces them to the last source column per class and of any class
 //      (9 registers), an exclusive maximum scan over the threads (stream.h: block_scan_exclusive) carries those across the row, and a
 //      sweep over the chunk writes, per pixel, the left candidate of its own class and of any class as 16-bit columns (0xFFFF: none):
 //      one 16-byte word per 4 pixels.
@@ -23,6 +24,7 @@
 #include "common.h"
 #include "metrics_decode.h"
 #include "refine_class.h"
+#include "refine_rows.h"
 #include "right_view.h"
 #include "stream.h"
 
@@ -33,14 +35,15 @@ using ss::metrics::LT_I64;     // label sources: the codes of every label_dtype
 using ss::metrics::LT_F32;
 using ss::refine::NCLS;        // classes 0 .. 7; NCLS itself stands for "none" (refine_class.h: class_of, classes4)
 using ss::refine::classes4;
+using ss::refine::NOCOL;        // refine_rows.h: the byte of a pixel, the choice
+using ss::refine::SCRATCH;
+using ss::refine::SRC;
+using ss::refine::choose;
 using ss::rview::MAX_W;
 using ss::rview::lr_diff;
 using ss::rview::map_shape;
 
 constexpr int GV = 2048;                 // workgroups of a pass
-constexpr int SRC = 16;                 // the source bit of a pixel's byte
-constexpr int NOCOL = 0xFFFF;            // no candidate (W <= 8192 < 0xFFFF)
-constexpr int SCRATCH = 48;              // ints of scan scratch: 4 waves x 9 values, each wave's rounded up to 12
 
 typedef unsigned char u8;
 
@@ -59,17 +62,6 @@ struct RefineArgs {
     int B, H, W, chunk;        // chunk: the columns of a thread in steps 2 and 3
     int max_gap, prefer, fallback;
 };
-
-// the candidate of a tier that wins at pixel x: L, R columns or NOCOL; -1 if neither lies within max_gap
-__device__ __forceinline__ int choose(int x, int L, int R, const float* d, int max_gap, int prefer) {
-    const bool hasL = L != NOCOL && x - L <= max_gap, hasR = R != NOCOL && R - x <= max_gap;
-    if (!(hasL && hasR)) return hasL ? L : (hasR ? R : -1);
-    const float dl = d[L], dr = d[R];
-    const int gl = x - L, gr = R - x;
-    const bool right = prefer == 0 ? (dr < dl) | ((dr == dl) & (gr < gl))        // background: the smaller disparity
-                                   : (gr < gl) | ((gr == gl) & (dr < dl));       // nearest
-    return right ? R : L;
-}
 
 // dynamic LDS: SCRATCH ints; the candidates, left then right, one 16-byte word per 4 columns (own-class x 4, any-class x 4 as 16-bit
 // columns): 2 x Wp / 4 words; Wp bytes
@@ -115,76 +107,7 @@ __global__ __launch_bounds__(BLOCK) void disparity_refine_k(RefineArgs a) {
             *reinterpret_cast<unsigned*>(flag + x0) = packed;
         }
         __syncthreads();
-        // 2 ---- the left candidates: the last source column per class (0 .. 7) and of any class (8), -1 for none
-        int last[NCLS + 1];
-#pragma unroll
-        for (int k = 0; k <= NCLS; ++k) last[k] = -1;
-        for (int g = 0; g < chunk; g += 4) {
-            const unsigned f4 = *reinterpret_cast<const unsigned*>(flag + c0 + g);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int f = (int)((f4 >> (8 * j)) & 255u), x = c0 + g + j;
-                if (f & SRC) {
-                    last[NCLS] = x;
-#pragma unroll
-                    for (int k = 0; k < NCLS; ++k) last[k] = (f & 15) == k ? x : last[k];
-                }
-            }
-        }
-        block_scan_exclusive<NCLS + 1, false>(last, -1, scratch);
-        for (int g = 0; g < chunk; g += 4) {
-            const unsigned f4 = *reinterpret_cast<const unsigned*>(flag + c0 + g);
-            unsigned own[4], any[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int f = (int)((f4 >> (8 * j)) & 255u), x = c0 + g + j;
-                int mine = -1;
-#pragma unroll
-                for (int k = 0; k < NCLS; ++k) mine = (f & 15) == k ? last[k] : mine;
-                own[j] = (unsigned)mine & 0xFFFFu, any[j] = (unsigned)last[NCLS] & 0xFFFFu;          // (-1 becomes NOCOL)
-                if (f & SRC) {
-                    last[NCLS] = x;
-#pragma unroll
-                    for (int k = 0; k < NCLS; ++k) last[k] = (f & 15) == k ? x : last[k];
-                }
-            }
-            cand[(c0 + g) >> 2] = make_uint4(own[0] | own[1] << 16, own[2] | own[3] << 16, any[0] | any[1] << 16, any[2] | any[3] << 16);
-        }
-        // 3 ---- the right candidates: the first source column per class and of any class, NOCOL for none
-        int first[NCLS + 1];
-#pragma unroll
-        for (int k = 0; k <= NCLS; ++k) first[k] = NOCOL;
-        for (int g = chunk - 4; g >= 0; g -= 4) {
-            const unsigned f4 = *reinterpret_cast<const unsigned*>(flag + c0 + g);
-#pragma unroll
-            for (int j = 3; j >= 0; --j) {
-                const int f = (int)((f4 >> (8 * j)) & 255u), x = c0 + g + j;
-                if (f & SRC) {
-                    first[NCLS] = x;
-#pragma unroll
-                    for (int k = 0; k < NCLS; ++k) first[k] = (f & 15) == k ? x : first[k];
-                }
-            }
-        }
-        block_scan_exclusive<NCLS + 1, true>(first, NOCOL, scratch);
-        for (int g = chunk - 4; g >= 0; g -= 4) {
-            const unsigned f4 = *reinterpret_cast<const unsigned*>(flag + c0 + g);
-            unsigned own[4], any[4];
-#pragma unroll
-            for (int j = 3; j >= 0; --j) {
-                const int f = (int)((f4 >> (8 * j)) & 255u), x = c0 + g + j;
-                int mine = NOCOL;
-#pragma unroll
-                for (int k = 0; k < NCLS; ++k) mine = (f & 15) == k ? first[k] : mine;
-                own[j] = (unsigned)mine, any[j] = (unsigned)first[NCLS];
-                if (f & SRC) {
-                    first[NCLS] = x;
-#pragma unroll
-                    for (int k = 0; k < NCLS; ++k) first[k] = (f & 15) == k ? x : first[k];
-                }
-            }
-            cand[QR + ((c0 + g) >> 2)] = make_uint4(own[0] | own[1] << 16, own[2] | own[3] << 16, any[0] | any[1] << 16, any[2] | any[3] << 16);
-        }
+#include "refine_rows_steps.inc"       // 2, 3 ---- the left and the right candidates
         __syncthreads();
         // 4 ---- max_gap, the tiers, the choice; the outputs
         if (a.out || a.kind || a.source) {

@@ -1,4 +1,4 @@
-// What the refinement kernels share (disparity_refine.hip, disparity_median.hip, disparity_speckle.hip): the class of a pixel -- ONE definition
+// What the refinement kernels share (disparity_refine.hip, disparity_fill2d.hip, disparity_median.hip, disparity_speckle.hip): the class of a pixel -- ONE definition
 // (include/semstereo_hip.h, "disparity refinement": class[x]), so the fill, the median and the speckle filter can never disagree on which surface a
 // pixel belongs to.
 #pragma once

@@ -1,4 +1,4 @@
-// What right_view.hip and disparity_refine.hip share: where a left pixel lands in the right view and the left-right difference of two
+// What right_view.hip, disparity_refine.hip and disparity_fill2d.hip share: where a left pixel lands in the right view and the left-right difference of two
 // estimates -- ONE definition each (include/semstereo_hip.h, "right-view ground truth"), so the check inside the refinement can never
 // differ from ss_lr_consistency_fwd's -- and the limits of the row kernels.
 #pragma once

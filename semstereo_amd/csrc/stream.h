@@ -1,4 +1,4 @@
-// What the streaming kernels share (loss.hip, metrics.hip, joint_metrics.hip, vis.hip, sample_prep.hip, right_view.hip, disparity_refine.hip, disparity_median.hip, disparity_speckle.hip, scene_tiles.hip).  They are all one kind of
+// What the streaming kernels share (loss.hip, metrics.hip, joint_metrics.hip, vis.hip, sample_prep.hip, right_view.hip, disparity_refine.hip, disparity_fill2d.hip, disparity_median.hip, disparity_speckle.hip, scene_tiles.hip).  They are all one kind of
 // kernel: BLOCK threads, a capped grid with a grid-stride loop, a lane takes 4 consecutive elements (one wide access where the address
 // allows, scalars otherwise), and a reduction goes thread -> wave (shuffles) -> LDS -> one partial per workgroup in the caller's
 // workspace -> a small finish launch that adds the partials in a fixed order.  No floating-point atomics anywhere: two calls on the

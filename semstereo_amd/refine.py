@@ -24,14 +24,24 @@ The definitions (include/semstereo_hip.h, "disparity refinement", is their one f
     an unfilled pixel; "consistent" bool.
 Nothing is interpolated, so the kernel and the composition agree bit for bit.
 
+axes="both" (include/semstereo_hip.h, "disparity refinement: fill along rows and columns", is the full statement): the same fill
+looking in four directions.  A pixel that is no source has up to four candidates per tier, in the order L, R (its row, within
+max_gap columns), U, D (its column, within max_gap rows -- `max_gap` an integer for both or a pair (columns, rows)); "background"
+takes the least (value, distance, order), "nearest" the least (distance, value, order), which with L and R alone is the rule above.
+"source" is the column and "source_row" (REFINE_KEYS_2D) the row the value came from.  CUDA float32 maps up to 8192 x 8192 run
+csrc/disparity_fill2d.hip -- four launches over tiles of FILL2D_TILE = 64 rows x 256 columns: classify and reduce, scan the tiles'
+summaries, sweep down and up, then the row kernel's own scans and the choice; nothing waits on the host -- everything else a
+composition of per-class cummax / cummin along both axes and gathers on the flattened image.  modules.PATH_COUNTS["fill2d_hip"] /
+["fill2d_torch"] count these calls; axes="rows" (the default) is the call above, on the same kernel, under the same counters.  Not
+built: diagonal directions, sub-pixel blending of candidates, a per-axis `prefer`, maps beyond 8192 on the kernel.
+
 median_disparity (include/semstereo_hip.h, "disparity refinement: class-aware median", is the full statement): per pixel the lower
 median of the valid pixels of its (2r + 1)^2 window that share its class (all valid pixels for a pixel of no class or with
 same_class=False), in the total order of the fp32 bit patterns; border windows are smaller, nothing is padded.  A pixel is replaced
 only if `where` admits it, it is valid itself or fill_holes is set, and the window holds at least min_count members; every other pixel
 passes through bit for bit.  CUDA float32 tensors with radius <= 2 run csrc/disparity_median.hip (a 16 x 64 tile with its halo in
 LDS, a fixed compare-exchange network per pixel), everything else a composition of shifted views and one sort of the integer keys;
-modules.PATH_COUNTS["median_hip"] / ["median_torch"] count the calls.  Not built: the column pass proper (fill_holes reaches
-r x iterations rows, no further), a weighted or bilateral median, sub-pixel blending, radii above 2 on the kernel.
+modules.PATH_COUNTS["median_hip"] / ["median_torch"] count the calls.  Not built: a weighted or bilateral median, sub-pixel blending, radii above 2 on the kernel.
 
 filter_speckles (include/semstereo_hip.h, "disparity refinement: speckle removal", is the full statement): two 4-neighbours of an
 image link if both are valid, their disparities differ by at most max_diff (one fp32 subtraction) and -- with same_class -- they are
@@ -55,10 +65,13 @@ from ._host import _nograd, count
 from ._lib import call, ptr, query_bytes
 
 REFINE_KEYS = ("disparity", "kind", "source", "consistent")
+REFINE_KEYS_2D = REFINE_KEYS + ("source_row",)       # what axes="both" can also name: the row the value came from
+AXES = ("rows", "both")
+FILL2D_TILE = (64, 256)                      # csrc/disparity_fill2d.hip: TR rows x TC columns of a workgroup; a wave owns TR / 4 rows
 NUM_CLASSES = 8                              # csrc/disparity_refine.hip: classes 0 .. 7, anything else is "none"
 MAX_WIDTH = 8192                             # ... and 9 bytes of LDS per column
 PREFER = {"background": 0, "nearest": 1}
-_DTYPES = {"disparity": torch.float32, "kind": torch.uint8, "source": torch.int32, "consistent": torch.bool}
+_DTYPES = {"disparity": torch.float32, "kind": torch.uint8, "source": torch.int32, "consistent": torch.bool, "source_row": torch.int32}
 _MAX_ELEMENTS = 2 ** 31
 MEDIAN_KEYS = ("disparity", "count")
 MEDIAN_TILE = (16, 64)                       # csrc/disparity_median.hip: TH x TW output pixels of a workgroup
@@ -88,12 +101,13 @@ def _classes(label):
     return torch.where(inside, cls, torch.full_like(cls, NUM_CLASSES))
 
 
-def _nearest(mask, x, W):
-    """Per pixel the largest column x' < x and the smallest x' > x with mask[x'] (int64 [B,H,W]; -1 and W for none)."""
-    left = torch.where(mask, x, torch.full_like(x, -1)).cummax(2).values
-    right = torch.where(mask, x, torch.full_like(x, W)).flip(2).cummin(2).values.flip(2)
-    none_l, none_r = torch.full_like(left[..., :1], -1), torch.full_like(right[..., :1], W)
-    return torch.cat([none_l, left[..., :-1]], 2), torch.cat([right[..., 1:], none_r], 2)
+def _nearest(mask, x, W, axis=2):
+    """Per pixel the largest index x' < x and the smallest x' > x along `axis` with mask[x'] (int64 [B,H,W]; -1 and W for none): x
+    the pixels' own index along that axis, W its length (axis 2: columns, axis 1: rows)."""
+    left = torch.where(mask, x, torch.full_like(x, -1)).cummax(axis).values
+    right = torch.where(mask, x, torch.full_like(x, W)).flip(axis).cummin(axis).values.flip(axis)
+    none_l, none_r = torch.full_like(left.narrow(axis, 0, 1), -1), torch.full_like(right.narrow(axis, 0, 1), W)
+    return torch.cat([none_l, left.narrow(axis, 0, W - 1)], axis), torch.cat([right.narrow(axis, 1, W - 1), none_r], axis)
 
 
 def _choose(d, x, L, R, W, max_gap, prefer):
@@ -109,9 +123,9 @@ def _choose(d, x, L, R, W, max_gap, prefer):
     return has_l | has_r, torch.where(take_r, R, L)
 
 
-def _refine_torch(d, dr, keep, label, lo, hi, threshold, max_gap, prefer, fallback, fill_value, want):
-    B, H, W = d.shape
-    x = torch.arange(W, device=d.device).view(1, 1, W).expand(B, H, W)
+def _sources(d, dr, keep, lo, hi, threshold):
+    """(source[x] of the definitions, {"consistent": the check's map} with a right map)."""
+    W = d.shape[2]
     src = (d >= lo) & (d < hi)
     if keep is not None:
         src = src & (keep != 0)
@@ -122,6 +136,79 @@ def _refine_torch(d, dr, keep, label, lo, hi, threshold, max_gap, prefer, fallba
         diff = torch.where(lands & (m >= lo) & (m < hi), (d - m).abs(), torch.full_like(d, float("inf")))
         out["consistent"] = diff <= threshold
         src = src & out["consistent"]
+    return src, out
+
+
+def _choose4(flat, cands, prefer):
+    """(a candidate exists, the winner's index y* W + x*) of one tier: the least of the candidates `cands` = [(exists, index into the
+    flattened image, distance)] in the order L, R, U, D, by (v, g, order) for prefer 0 and (g, v, order) for prefer 1 -- a fold in
+    that order in which a later candidate wins only where it is strictly less."""
+    shape = cands[0][1].shape
+    has, idx, g = cands[0]
+    v = flat.gather(1, idx.reshape(shape[0], -1)).view(shape)
+    for has_c, idx_c, g_c in cands[1:]:
+        v_c = flat.gather(1, idx_c.reshape(shape[0], -1)).view(shape)
+        if prefer == 0:
+            later = (v_c < v) | ((v_c == v) & (g_c < g))
+        else:
+            later = (g_c < g) | ((g_c == g) & (v_c < v))
+        take = has_c & (~has | later)
+        has, idx, g, v = has | has_c, torch.where(take, idx_c, idx), torch.where(take, g_c, g), torch.where(take, v_c, v)
+    return has, idx
+
+
+def _fill2d_torch(d, dr, keep, label, lo, hi, threshold, gap_x, gap_y, prefer, fallback, fill_value, want):
+    """The definitions of include/semstereo_hip.h, "disparity refinement: fill along rows and columns": per class a cummax / cummin
+    along both axes, gathers on the flattened image, one lexicographic four-way choice per tier."""
+    B, H, W = d.shape
+    x = torch.arange(W, device=d.device).view(1, 1, W).expand(B, H, W)
+    y = torch.arange(H, device=d.device).view(1, H, 1).expand(B, H, W)
+    src, out = _sources(d, dr, keep, lo, hi, threshold)
+    if not {"disparity", "kind", "source", "source_row"} & set(want):
+        return out
+    flat = d.reshape(B, H * W)
+
+    def tier(L, R, U, Dn):
+        return _choose4(flat, [((L >= 0) & (x - L <= gap_x), y * W + L.clamp(min=0), x - L),
+                               ((R < W) & (R - x <= gap_x), y * W + R.clamp(max=W - 1), R - x),
+                               ((U >= 0) & (y - U <= gap_y), U.clamp(min=0) * W + x, y - U),
+                               ((Dn < H) & (Dn - y <= gap_y), Dn.clamp(max=H - 1) * W + x, Dn - y)], prefer)
+    here = y * W + x
+    has1, s1 = torch.zeros_like(src), here
+    if label is not None:
+        cls = _classes(label)
+        L, R, U, Dn = torch.full_like(x, -1), torch.full_like(x, W), torch.full_like(x, -1), torch.full_like(x, H)
+        for c in range(NUM_CLASSES):                    # per class and axis a cummax / cummin; a pixel takes those of its own class
+            mine = cls == c
+            (l, r), (u, dn) = _nearest(src & mine, x, W), _nearest(src & mine, y, H, axis=1)
+            L, R, U, Dn = torch.where(mine, l, L), torch.where(mine, r, R), torch.where(mine, u, U), torch.where(mine, dn, Dn)
+        has1, s1 = tier(L, R, U, Dn)
+    filled1 = ~src & has1
+    if fallback:
+        has2, s2 = tier(*_nearest(src, x, W), *_nearest(src, y, H, axis=1))
+        filled2 = ~src & ~has1 & has2
+    else:
+        filled2, s2 = torch.zeros_like(src), s1
+    index = torch.where(src, here, torch.where(filled1, s1, torch.where(filled2, s2, torch.full_like(x, -1))))
+    found = index >= 0
+    row = torch.div(index.clamp(min=0), W, rounding_mode="floor")
+    if "source" in want:
+        out["source"] = torch.where(found, index.clamp(min=0) - row * W, index).to(torch.int32)
+    if "source_row" in want:
+        out["source_row"] = torch.where(found, row, index).to(torch.int32)
+    if "kind" in want:
+        kind = torch.where(src, 0, torch.where(filled1, 1, torch.where(filled2, 2, 3)))
+        out["kind"] = kind.to(torch.uint8)
+    if "disparity" in want:
+        picked = flat.gather(1, index.clamp(min=0).reshape(B, -1)).view(B, H, W)
+        out["disparity"] = torch.where(found, picked, torch.full_like(d, fill_value))
+    return out
+
+
+def _refine_torch(d, dr, keep, label, lo, hi, threshold, max_gap, prefer, fallback, fill_value, want):
+    B, H, W = d.shape
+    x = torch.arange(W, device=d.device).view(1, 1, W).expand(B, H, W)
+    src, out = _sources(d, dr, keep, lo, hi, threshold)
     if not {"disparity", "kind", "source"} & set(want):
         return out
     has1, s1 = torch.zeros_like(src), torch.full_like(x, -1)
@@ -151,7 +238,21 @@ def _refine_torch(d, dr, keep, label, lo, hi, threshold, max_gap, prefer, fallba
     return out
 
 
-def _refine(disparity, disp_right, label, keep, threshold, maxdisp, disp_range, max_gap, prefer, fallback, fill_value, want, keys):
+def _gap(value, most, what):
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or int(value) != value or value < 1:
+        raise ValueError(f"{what} is an integer >= 1, got {value!r}")
+    return min(int(value), max(most, 1))
+
+
+def _refine(disparity, disp_right, label, keep, threshold, maxdisp, disp_range, max_gap, prefer, fallback, fill_value, want, keys,
+            axes="rows"):
+    if axes not in AXES:
+        raise ValueError(f"axes is one of {AXES}, got {axes!r}")
+    both = axes == "both"
+    if both:
+        keys = keys + ("source_row",)
+    elif isinstance(max_gap, (tuple, list)):
+        raise ValueError(f'max_gap is a pair (columns, rows) only with axes="both", got {max_gap!r}')
     want = tuple(want)
     if not want or not set(want) <= set(keys):
         raise ValueError(f"want names some of {keys}, got {want}")
@@ -177,18 +278,44 @@ def _refine(disparity, disp_right, label, keep, threshold, maxdisp, disp_range, 
         disparity = disparity.unsqueeze(0)
         disp_right, label, keep = (None if t is None else t.unsqueeze(0) for t in (disp_right, label, keep))
     B, H, W = disparity.shape
-    if max_gap is None:
-        max_gap = W
-    if isinstance(max_gap, bool) or int(max_gap) != max_gap or max_gap < 1:
-        raise ValueError(f"max_gap is an integer >= 1, got {max_gap!r}")
-    max_gap = min(int(max_gap), max(W, 1))
+    if both:
+        pair = (W, H) if max_gap is None else tuple(max_gap) if isinstance(max_gap, (tuple, list)) else (max_gap, max_gap)
+        if len(pair) != 2:
+            raise ValueError(f"max_gap is an integer or a pair (columns, rows), got {max_gap!r}")
+        gap_x, gap_y = _gap(pair[0], W, "max_gap (columns)"), _gap(pair[1], H, "max_gap (rows)")
+    else:
+        if max_gap is None:
+            max_gap = W
+        if isinstance(max_gap, bool) or int(max_gap) != max_gap or max_gap < 1:
+            raise ValueError(f"max_gap is an integer >= 1, got {max_gap!r}")
+        max_gap = min(int(max_gap), max(W, 1))
     fill_value = float(np.float32(fill_value))
     if keep is not None and keep.dtype == torch.bool:
         keep = keep.view(torch.uint8) if keep.is_contiguous() else keep.to(torch.uint8)
     how = None if label is None else D._label_for_kernel(label, disparity)
     floats = [disparity] + ([disp_right] if disp_right is not None else [])
     dense = floats + ([keep] if keep is not None else [])
-    if (all(t.dtype == torch.float32 for t in floats) and (keep is None or keep.dtype == torch.uint8) and _hip(*dense)
+    if both:
+        if (all(t.dtype == torch.float32 for t in floats) and (keep is None or keep.dtype == torch.uint8) and _hip(*dense)
+                and W <= MAX_WIDTH and H <= MAX_WIDTH and 0 < disparity.numel() < _MAX_ELEMENTS and (label is None or how is not None)):
+            count("fill2d_hip")
+            dev = disparity.device
+            code, row, img = how if how is not None else (0, W, H * W)
+            nbytes = query_bytes("ss_disparity_fill2d_scratch", B, H, W)
+            with torch.cuda.device(dev):
+                scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+                out = {k: torch.empty((B, H, W), dtype=_DTYPES[k], device=dev) for k in want}
+                call("ss_disparity_fill2d_fwd", ptr(disparity), ptr(disp_right), ptr(keep), ptr(label), code, row, img, B, H, W, lo, hi,
+                     threshold, gap_x, gap_y, PREFER[prefer], int(bool(fallback)), fill_value, ptr(scratch), nbytes,
+                     *(ptr(out.get(k)) for k in ("disparity", "kind", "source", "source_row", "consistent")))
+        elif disparity.numel() == 0:
+            count("fill2d_torch")
+            out = {k: torch.empty((B, H, W), dtype=_DTYPES[k], device=disparity.device) for k in want}
+        else:
+            count("fill2d_torch")
+            out = _fill2d_torch(disparity.to(torch.float32).contiguous(), None if disp_right is None else disp_right.to(torch.float32),
+                                keep, label, lo, hi, threshold, gap_x, gap_y, PREFER[prefer], bool(fallback), fill_value, want)
+    elif (all(t.dtype == torch.float32 for t in floats) and (keep is None or keep.dtype == torch.uint8) and _hip(*dense)
             and W <= MAX_WIDTH and 0 < disparity.numel() < _MAX_ELEMENTS and (label is None or how is not None)):
         count("refine_hip")
         dev = disparity.device
@@ -207,7 +334,7 @@ def _refine(disparity, disp_right, label, keep, threshold, maxdisp, disp_range, 
 
 @_nograd
 def fill_disparity(disparity, label=None, keep=None, maxdisp=None, disp_range=None, max_gap=None, prefer="background", fallback=True,
-                   fill_value=-999.0, want=("disparity", "kind")):
+                   fill_value=-999.0, want=("disparity", "kind"), axes="rows"):
     """The holes of a disparity map filled row by row from the surface they belong to (the module's definitions).  `disparity`
     [B,H,W] (or [H,W]) float32 -- anything else is converted first; `label` of any dtype: the class of every pixel, without it every
     pixel is of no class and only tier 2 fills; `keep`: a bool / uint8 mask of the pixels that may serve as sources (the `consistent`
@@ -215,21 +342,26 @@ def fill_disparity(disparity, label=None, keep=None, maxdisp=None, disp_range=No
     names the values that are sources at all; `max_gap` (default: the row's width) bounds how far a value may travel; `prefer` is
     "background" or "nearest"; `fallback=False` leaves what the own class cannot fill.  `want` names some of ("disparity", "kind",
     "source").  Returns a dictionary of tensors on the input's device; nothing waits on the host.  An argument that makes no sense
-    is a ValueError before any launch."""
-    return _refine(disparity, None, label, keep, 0.0, maxdisp, disp_range, max_gap, prefer, fallback, fill_value, want, REFINE_KEYS[:3])
+    is a ValueError before any launch.
+
+    `axes="both"` looks along the columns too (the module's paragraph on the two-axis fill): the candidates are the nearest sources
+    to the left, to the right, above and below; `max_gap` may then be a pair (columns, rows) (default: the map's width and height)
+    and `want` may name "source_row"."""
+    return _refine(disparity, None, label, keep, 0.0, maxdisp, disp_range, max_gap, prefer, fallback, fill_value, want, REFINE_KEYS[:3],
+                   axes)
 
 
 @_nograd
 def refine_disparity(disp_left, disp_right, label=None, threshold=1.0, keep=None, maxdisp=None, disp_range=None, max_gap=None,
-                     prefer="background", fallback=True, fill_value=-999.0, want=("disparity", "kind")):
+                     prefer="background", fallback=True, fill_value=-999.0, want=("disparity", "kind"), axes="rows"):
     """The left-right check and the fill in one pass: a pixel of `disp_left` is a source only if it is also consistent with
     `disp_right` (data.lr_consistency's definition and arguments: `disp_right[r]` is the disparity of RIGHT pixel r,
     `-model(right, left)` for a model; `threshold` in pixels), everything else is filled as fill_disparity does.  `want` may also name
-    "consistent", the bool map of the check."""
+    "consistent", the bool map of the check.  `axes="both"`: as for fill_disparity."""
     if disp_right is None:
         raise ValueError("refine_disparity takes two estimates; fill_disparity takes one")
     return _refine(disp_left, disp_right, label, keep, threshold, maxdisp, disp_range, max_gap, prefer, fallback, fill_value, want,
-                   REFINE_KEYS)
+                   REFINE_KEYS, axes)
 
 
 def _keys(d):

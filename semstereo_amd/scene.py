@@ -42,7 +42,7 @@ from ._lib import call, ptr
 OUTPUTS = ("disparity", "logits", "label", "spread", "count")
 #: what SceneStereo(refine=...) adds: the right view's mosaic (minus the swapped pair's), the check and the filled mosaic
 REFINED_OUTPUTS = ("disparity_right", "consistent", "disparity_refined", "kind", "disparity_median", "speckle")
-_REFINE_ARGS = ("maxdisp", "disp_range", "threshold", "max_gap", "prefer", "fallback", "fill_value", "median", "speckle")
+_REFINE_ARGS = ("maxdisp", "disp_range", "threshold", "max_gap", "prefer", "fallback", "fill_value", "axes", "median", "speckle")
 #: refine=dict(..., speckle=dict(...)): filter_speckles' arguments
 _SPECKLE_ARGS = ("max_size", "max_diff", "same_class")
 #: refine=dict(..., median=dict(...)): median_disparity's arguments, and which pixels may change ("filled": kind != 0; "all")
@@ -308,8 +308,8 @@ class SceneStereo:
     that sees it well inside, so overlap_x of about 2 * maxdisp with the default ramp (= the overlap) is the sensible setting; the
     default (256, 256) suits maxdisp = 128.  `spread` shows where the tiles still disagree.
 
-    The left-right check per scene: with `refine=dict(maxdisp=, threshold=, max_gap=, prefer=, fallback=)` (refine_disparity's
-    arguments) `want` may also name "disparity_right", "consistent", "disparity_refined" and "kind".  If it does, every tile row is also
+    The left-right check per scene: with `refine=dict(maxdisp=, threshold=, max_gap=, prefer=, fallback=, axes=)` (refine_disparity's
+    arguments; `axes="both"` fills along rows and columns) `want` may also name "disparity_right", "consistent", "disparity_refined" and "kind".  If it does, every tile row is also
     issued with the views swapped -- the same windows, `model(right_tile, left_tile)` -- and those disparities are blended into a second
     mosaic band by band alongside the first.  The blend of negated tiles is the exact negation of the blend (products, sums and the
     division are sign-symmetric), so that mosaic is negated once, in place, after the last band: "disparity_right", the form
